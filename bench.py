@@ -10,11 +10,19 @@ metrics + the 4x150x150 u8 observation raster, followed by the auto-reset of the
 reset is a copy of the trial's settled template (each trial's 1000 settle sub-steps run once, at load: reset() is a pure
 function of the trial when cfg.random_start is off -- tested identical to settling in place) plus its first observation.
 Inputs (scenarios, actions) are resident in HBM before the timed region.  `value` is measured from freshly reset episodes
-(steps W..W+K); `steady_state` repeats the measurement with the envs spread uniformly over the phases of an episode.
+(steps W..W+K).
 Multi-GPU: environments shard over ranks (4096 per GPU, weak scaling, no data-path collective); the only collective is the
 all-gather of the [E/R, 6] episode-metric rows after the timed region (RCCL over xGMI).  For N > 1 the line also carries
-`allgather_ms` (median of 20 timed gathers of the real block on device tensors) and `strong_scaling` (a second timed region with
-the same 4096 envs split over the N ranks: value, ms_per_step, speed-up and efficiency against this run's own one-GPU time).
+`allgather_ms` (median of 20 timed gathers of the real block on device tensors).
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds the measurements that take runs of their own:
+`steady_state` (the measurement repeated with the envs spread uniformly over the phases of an episode), the CPU baselines and, for
+N > 1, `strong_scaling` (a second timed region with the same 4096 envs split over the N ranks: value, ms_per_step, speed-up and
+efficiency against this run's own one-GPU time).
+
+`--dump-outputs DIR` writes what the last timed step handed its caller (after that step's auto-reset) as DIR/<name>.npy: reward,
+terminated, truncated and info of every env, and the observations of a fixed, seeded sample of envs (obs_env_ids.npy names them).
+Scenarios and actions are seeded, so the same arguments give the same inputs on every run.
 
     --config c2 (default)  BASELINE.json configs[1]: 4096 envs per GPU, 30 % concentration
     --config c5            BASELINE.json configs[4]: 4096 envs per GPU, 50 % concentration (32 768 envs on 8 GPUs)
@@ -288,6 +296,34 @@ def _check_errors(env):
 
 _IGNORED_ERRORS = False
 
+DUMP_OBS_BYTES = 48 << 20     # budget of the observation sample; the per-env arrays beside it stay well below the 64 MB of the whole dump
+
+
+def dump_outputs(directory, step_out):
+    """Write the tensors env.step() returned in the last timed step (obs, reward, terminated, truncated, info; obs and info as the auto-reset
+    left them) as <directory>/<name>.npy.  float64 and integer tensors wider than 16 bits become float64, the rest float32 (exact either way).
+    The observations are all envs' when they fit DUMP_OBS_BYTES as float32, else those of a fixed, seeded sample of envs (obs_env_ids.npy)."""
+    os.makedirs(directory, exist_ok=True)
+    obs, rew, term, trunc, info = step_out
+
+    def host(t):
+        wide = t.dtype in (torch.float64, torch.int32, torch.int64)
+        return t.detach().cpu().numpy().astype(np.float64 if wide else np.float32)
+
+    E = int(obs.shape[0])
+    per_env = int(np.prod(obs.shape[1:])) * 4
+    if E * per_env <= DUMP_OBS_BYTES:
+        ids = np.arange(E)
+    else:
+        ids = np.sort(np.random.default_rng(0).choice(E, DUMP_OBS_BYTES // per_env, replace=False))
+    arrays = {"obs": host(obs[torch.from_numpy(ids).to(obs.device)]), "obs_env_ids": ids.astype(np.float64),
+              "reward": host(rew), "terminated": host(term), "truncated": host(trunc), "info": host(info)}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, "output dump of %d bytes exceeds 64 MB" % total
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    print("bench.py: wrote %s (%.1f MB, obs of %d of %d envs)" % (", ".join(sorted(arrays)), total / 1e6, len(ids), E), file=sys.stderr)
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -298,10 +334,14 @@ def main():
     ap.add_argument("--concentration", type=float, default=0.3)
     ap.add_argument("--trials", type=int, default=100)
     ap.add_argument("--config", default="c2", choices=["c2", "c5"], help="c2 = BASELINE.json configs[1] (30 %%), c5 = configs[4] (50 %%, 4096 envs per GPU)")
-    ap.add_argument("--no-steady-state", action="store_true", help="skip the staggered-phase (steady-state) measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beside the headline: steady state, CPU baselines, strong scaling (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    ap.add_argument("--no-steady-state", action="store_true", help="--full: skip the staggered-phase (steady-state) measurement")
     ap.add_argument("--steady-steps", type=int, default=30)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-strong", action="store_true", help="N > 1: skip the strong-scaling region (E envs split over the ranks)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-strong", action="store_true", help="--full, N > 1: skip the strong-scaling region (E envs split over the ranks)")
     ap.add_argument("--no-auto-reset", action="store_true")
     ap.add_argument("--env", default="ship-ice", choices=["ship-ice", "maze", "box", "area"],
                     help="ship-ice = BASELINE.json configs[1] (the headline); maze = configs[2], box = configs[3] (box-delivery-v0, "
@@ -375,14 +415,19 @@ def main():
     PH = 40                                                       # phases of the staggered (steady-state) measurement
     KS = 0 if (args.no_steady_state or args.env != "ship-ice") else args.steady_steps
     extra = (PH + KS) if KS > 0 else 0
+    # the stream has the same shape with or without --full: the values torch.rand draws can depend on the size of the tensor, and the timed steps
+    # of a plain run get the same actions as those of a --full run
     actions = (torch.rand((K + W + extra, E), generator=g, device=device, dtype=torch.float64) * 2 - 1).float().double()
+    if not args.full:
+        KS = 0
 
     env.reset()
     ep_done = torch.zeros(E, dtype=torch.int64, device=device)
     ep_success = torch.zeros(E, dtype=torch.int64, device=device)
+    last = {}
 
     def one_step(t):
-        obs, rew, term, trunc, info = env.step(actions[t])
+        obs, rew, term, trunc, info = last["out"] = env.step(actions[t])
         if not args.no_auto_reset:
             ep_done.add_(term.to(torch.int64))
             if args.env in ("box", "area"):   # success = every box delivered / cleared (terminated without the truncation)
@@ -413,6 +458,8 @@ def main():
     cost_stats = env.cost_stats() if (args.env in ("ship-ice", "maze") and hasattr(env, "cost_stats") and hasattr(env.L, "bp_get_cost_stats")) else None
     env.enable_timing(False)
     _check_errors(env)
+    if args.dump_outputs and rank == 0 and K > 0:
+        dump_outputs(args.dump_outputs, last["out"])
     # clock the chip held over the timed region: shader-clock counter against the 100 MHz reference, both stamped on the device after every step
     clk1 = env.clock_stamps() if clk0 is not None else None
     # both stamps of the pair come from ONE XCD (the shader-clock counters of different XCDs are not synchronised): the XCD with the longest span
@@ -486,7 +533,7 @@ def main():
     # ---- strong scaling: the SAME total of E envs split over the ranks, E / world per GPU, on the same ranks;
     #      T1 is this run's own weak region (every rank stepped E envs on one GPU), so speed-up = T1 / T_N and efficiency = speed-up / world ----
     strong = None
-    if dist is not None and args.env == "ship-ice" and not args.no_strong and E % world == 0:
+    if args.full and dist is not None and args.env == "ship-ice" and not args.no_strong and E % world == 0:
         Es = E // world
         env_s = BatchedShipIceEnv(Es, cfg={"concentration": args.concentration}, trials=trials, device=device, env_id_offset=rank * Es)
         env_s.reset()
@@ -686,11 +733,11 @@ def main():
                                        "this workload and two thirds of its time -- that is the reference's own loop, not kernel overhead.  The other kind -- execute_robot_path into "
                                        "STEP_LIMIT with a robot that pushes against a wall -- recurs bit for bit and is skipped exactly (straggler_env_steps.sim_steps_skipped_by_them)")
             out["substeps_per_s"] = None
-        if world == 1 and not args.no_cpu_baseline and args.env == "ship-ice":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.env == "ship-ice":
             out["cpu_baseline"] = cpu_baseline(env, trials)
             out["cpu_baseline"]["single_thread"] = cpu_baseline_single_thread(env)
             out["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]
-        if world == 1 and not args.no_cpu_baseline and args.env in ("box", "area", "maze"):
+        if args.full and world == 1 and not args.no_cpu_baseline and args.env in ("box", "area", "maze"):
             out["cpu_baseline"] = {"box": cpu_baseline_box, "area": cpu_baseline_area, "maze": cpu_baseline_maze}[args.env](env, trials)
             out["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]
         if _IGNORED_ERRORS:

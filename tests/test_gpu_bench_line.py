@@ -25,7 +25,7 @@ def _bench(*args):
 
 
 def test_small_ship_ice_line_has_the_contract_keys_and_the_ceilings():
-    d = _bench("--envs-per-gpu", "256", "--trials", "8", "--steps", "4", "--warmup", "2", "--steady-steps", "3", "--no-cpu-baseline")
+    d = _bench("--full", "--envs-per-gpu", "256", "--trials", "8", "--steps", "4", "--warmup", "2", "--steady-steps", "3", "--no-cpu-baseline")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline"):
         assert k in d, k
     assert d["n_gpus"] == 1 and d["steps"] == 4 and d["warmup"] == 2 and d["dtype"] == "f64" and d["vs_baseline"] is None and d["value"] > 0
@@ -41,3 +41,25 @@ def test_small_ship_ice_line_has_the_contract_keys_and_the_ceilings():
     assert c["launch_over_chain"] >= 0.98 and c["launch_over_work"] >= c["launch_over_chain"]
     assert 1000 < r["clock_mhz"] < 3500 and r["clock_span_ms"] > 0
     assert any(x["xcd"] is not None and x["span_ms"] > 0 for x in r["clock_per_xcd"])
+
+
+def test_plain_line_is_lean_and_its_output_dump_repeats(tmp_path):
+    """Without --full the line carries the headline only (no steady state, no CPU baseline); --steps sets the number of timed launches; --dump-outputs
+    writes the last timed step's outputs as float32 / float64 .npy files within 64 MB, and a second run with the same arguments writes the same arrays."""
+    import numpy as np
+    dumps = []
+    for run in range(2):
+        d = _bench("--envs-per-gpu", "256", "--trials", "8", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / str(run)))
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0 and d["roofline"]["ceiling"]["launches"] == 3
+        assert not {"steady_state", "steady_state_value", "cpu_baseline", "gpu_over_cpu", "strong_scaling"} & set(d)
+        files = sorted(os.listdir(tmp_path / str(run)))
+        assert files == ["info.npy", "obs.npy", "obs_env_ids.npy", "reward.npy", "terminated.npy", "truncated.npy"], files
+        arrs = {f: np.load(tmp_path / str(run) / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        assert arrs["reward.npy"].shape == (256,) and arrs["obs.npy"].shape[1:] == (4, 150, 150) and arrs["obs.npy"].any()
+        dumps.append(arrs)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f

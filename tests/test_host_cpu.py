@@ -331,3 +331,39 @@ def test_log_obs_png_codec_and_render_log_obs_refusal(tmp_path):
             refuse_render_log_obs(merge_user_cfg(default_cfg(name), {"render": {"log_obs": True}}), name)
     for name in ("ship_ice", "maze_namo"):
         assert default_cfg(name).log_obs is False
+
+
+def test_bench_output_dump_is_float_bounded_and_seeded(tmp_path, monkeypatch):
+    """bench.py --dump-outputs (CPU tensors here): the five outputs of env.step as float32 / float64 .npy files, exact; the observations of all envs when
+    they fit the budget, else of a seeded sample that is the same on every call; at the default budget a 4096-env dump stays within 64 MB."""
+    import importlib.util
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_dump", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    E, shape = 64, (4, 15, 15)
+    g = torch.Generator().manual_seed(0)
+    out = (torch.randint(0, 256, (E,) + shape, generator=g, dtype=torch.uint8), torch.rand(E, generator=g, dtype=torch.float64),
+           torch.randint(0, 2, (E,), generator=g, dtype=torch.uint8), torch.zeros(E, dtype=torch.uint8), torch.rand((E, 10), generator=g, dtype=torch.float64))
+    bench.dump_outputs(str(tmp_path / "all"), out)
+    a = {n: np.load(tmp_path / "all" / (n + ".npy")) for n in ("obs", "obs_env_ids", "reward", "terminated", "truncated", "info")}
+    assert a["obs"].dtype == np.float32 and a["reward"].dtype == np.float64 and a["terminated"].dtype == np.float32 and a["info"].dtype == np.float64
+    assert np.array_equal(a["obs"], out[0].numpy()) and np.array_equal(a["reward"], out[1].numpy()) and np.array_equal(a["info"], out[4].numpy())
+    assert np.array_equal(a["obs_env_ids"], np.arange(E))
+    monkeypatch.setattr(bench, "DUMP_OBS_BYTES", 10 * int(np.prod(shape)) * 4)
+    ids = []
+    for run in ("s0", "s1"):
+        bench.dump_outputs(str(tmp_path / run), out)
+        i = np.load(tmp_path / run / "obs_env_ids.npy").astype(np.int64)
+        assert len(i) == 10 and np.all(np.diff(i) > 0)
+        assert np.array_equal(np.load(tmp_path / run / "obs.npy"), out[0].numpy()[i])
+        ids.append(i)
+    assert np.array_equal(ids[0], ids[1])
+    monkeypatch.undo()
+    per_env_f32 = 4 * 150 * 150 * 4
+    assert (bench.DUMP_OBS_BYTES // per_env_f32) * per_env_f32 + 4096 * (8 + 4 + 4 + 8 * 32 + 8) <= 64 << 20
+
+
+def test_bench_has_the_full_and_dump_options():
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
+    assert p.returncode == 0 and "--full" in p.stdout.decode() and "--dump-outputs" in p.stdout.decode()

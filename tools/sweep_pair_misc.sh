@@ -1,5 +1,5 @@
 run() { local label=$1; shift; local out=$(env "$@" 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(round(d['value']), round(d['roofline']['physics_ms'],3), round(d.get('steady_state',{}).get('value',0)), d.get('invalid'))"); echo "$label $out"; }
-B="python bench.py --steps 30 --warmup 5 --no-cpu-baseline"
+B="python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline"
 run "c2 pair default" BP_X=0 $B
 for ch in 25 34 50 67; do run "c2 pair chunk=$ch" BP_SCHED=$ch $B; done
 run "c2 nopair" BP_PAIR=0 $B
