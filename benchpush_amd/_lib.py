@@ -26,7 +26,8 @@ EXPORTS = ["bp_abi_version", "bp_create", "bp_destroy", "bp_load_scenarios", "bp
            "bp_bd_create", "bp_bd_load", "bp_bd_sizeof_config", "bp_bd_get_maps", "bp_bd_get_state",
            "bp_get_episode_metrics", "bp_get_episode_history", "bp_start_uniform", "bp_debug_round2", "bp_debug_scramble_hints",
            "bp_copy_rows_masked", "bp_pair_mode", "bp_get_pair_stats", "bp_bd_get_stragglers",
-           "bp_device_shared", "bp_launch_policy_query", "bp_bd_budget", "bp_get_cost_stats", "bp_bd_get_cycle_skips"]
+           "bp_device_shared", "bp_launch_policy_query", "bp_bd_budget", "bp_get_cost_stats", "bp_bd_get_cycle_skips",
+           "bp_sizeof_render_args", "bp_sizeof_render_prim", "bp_set_render_table", "bp_render"]
 
 
 class BpCostmapConfig(C.Structure):
@@ -164,6 +165,14 @@ def load():
     L.bp_bd_load.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, vp, vp]
     L.bp_bd_get_maps.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, vp]
     L.bp_bd_get_state.argtypes = [vp, vp, vp, vp]
+    if hasattr(L, "bp_render"):
+        from .render import RenderArgs, RenderPrim
+        L.bp_sizeof_render_args.restype = C.c_int32
+        L.bp_sizeof_render_prim.restype = C.c_int32
+        if L.bp_sizeof_render_args() != C.sizeof(RenderArgs) or L.bp_sizeof_render_prim() != C.sizeof(RenderPrim):
+            raise BpError("bp_render_args / bp_render_prim layout mismatch between benchpush_amd.render and the library")
+        L.bp_set_render_table.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp]
+        L.bp_render.argtypes = [vp, C.POINTER(RenderArgs), vp, C.c_int32, vp, vp, vp, vp]
     _lib = L
     return L
 

@@ -19,6 +19,7 @@
 #include "bp_host_bd.hpp"
 #include "bp_boxdelivery.hpp"
 #include "bp_policy.hpp"
+#include "bp_render.hpp"
 
 struct bp_handle {
     bp_config cfg;
@@ -72,6 +73,12 @@ struct bp_handle {
     size_t ev_used = 0;
     unsigned long long *cost_ring = nullptr;   // [BP_COST_RING][2] per-launch (sum, max) of the envs' step cycles while timing is on (k_cost_stats)
     int cost_n = 0;
+    // rgb_array frames (bp_set_render_table / bp_render)
+    int *r_order = nullptr;           // [T][nbcap] slots bottom first
+    unsigned *r_rgb = nullptr;        // [T][nbcap]
+    bp_render_prim *r_prims = nullptr;// [BP_RENDER_MAX_PRIMS], layer 0 first
+    int r_nunder = 0, r_nover = 0;
+    bool r_table = false;
 };
 #define BP_COST_RING 1024
 
@@ -1576,6 +1583,91 @@ int bp_bd_get_state(bp_handle *h, uint8_t *alive, double *waypoints, int32_t *nw
     if (alive) HIPCHK(h, hipMemcpy(alive, h->Q.alive, E * BD_MAXBOX, hipMemcpyDeviceToHost));
     if (waypoints) HIPCHK(h, hipMemcpy(waypoints, h->Q.wp, sizeof(double) * E * BD_MAXWP * 3, hipMemcpyDeviceToHost));
     if (nwp) HIPCHK(h, hipMemcpy(nwp, h->Q.nwp, sizeof(int) * E, hipMemcpyDeviceToHost));
+    return BP_OK;
+}
+
+int32_t bp_sizeof_render_args(void) { return (int32_t)sizeof(bp_render_args); }
+int32_t bp_sizeof_render_prim(void) { return (int32_t)sizeof(bp_render_prim); }
+
+int bp_set_render_table(bp_handle *h, int32_t T, int32_t nslot, const int32_t *order, const uint32_t *rgb, int32_t nprim, const bp_render_prim *prims)
+{
+    if (!h) return BP_EINVAL;
+    if (!h->loaded) return fail(h, BP_ESTATE, "render table before the scenarios are loaded");
+    if (!order || !rgb || T != h->num_trials || nslot != h->nbcap)
+        return fail(h, BP_EINVAL, "render table: order / rgb must be [num_trials][nb_cap] host arrays");
+    if (nprim < 0 || nprim > BP_RENDER_MAX_PRIMS || (nprim > 0 && !prims)) return fail(h, BP_EINVAL, "render table: 0 <= nprim <= BP_RENDER_MAX_PRIMS");
+    std::vector<bp_render_prim> pr;
+    for (int layer = 0; layer < 2; layer++)
+        for (int i = 0; i < nprim; i++) {
+            const bp_render_prim &p = prims[i];
+            if (p.layer != 0 && p.layer != 1) return fail(h, BP_EINVAL, "render primitive: layer must be 0 or 1");
+            if (!((p.kind == 0 && p.nv >= 3 && p.nv <= BP_RENDER_PRIM_VERTS) || (p.kind == 1 && p.nv == 2)))
+                return fail(h, BP_EINVAL, "render primitive: a polygon has 3..8 vertices, a capsule 2");
+            if (p.layer == layer) pr.push_back(p);
+        }
+    const size_t n = (size_t)T * nslot;
+    for (size_t i = 0; i < n; i++)
+        if (order[i] < -1 || order[i] >= nslot) return fail(h, BP_EINVAL, "render table: slot index out of range");
+    BP_DEVICE(h);
+    int rc;
+    if (!h->r_order) {
+        if ((rc = dalloc(h, &h->r_order, n))) return rc;
+        if ((rc = dalloc(h, &h->r_rgb, n))) return rc;
+        if ((rc = dalloc(h, &h->r_prims, BP_RENDER_MAX_PRIMS))) return rc;
+    }
+    HIPCHK(h, hipMemcpy(h->r_order, order, sizeof(int) * n, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(h->r_rgb, rgb, sizeof(unsigned) * n, hipMemcpyHostToDevice));
+    if (!pr.empty()) HIPCHK(h, hipMemcpy(h->r_prims, pr.data(), sizeof(bp_render_prim) * pr.size(), hipMemcpyHostToDevice));
+    h->r_nunder = 0;
+    for (const bp_render_prim &p : pr) h->r_nunder += p.layer == 0;
+    h->r_nover = (int)pr.size() - h->r_nunder;
+    h->r_table = true;
+    return BP_OK;
+}
+
+int bp_render(bp_handle *h, const bp_render_args *args, const int32_t *env_ids, int32_t k, const double *paths, const int32_t *path_len,
+              uint8_t *out, void *stream)
+{
+    if (!h) return BP_EINVAL;
+    if (!args || !env_ids || !out) return fail(h, BP_EINVAL, "bp_render: null args, env_ids or out");
+    if (k <= 0) return fail(h, BP_EINVAL, "bp_render: k must be positive");
+    const bp_render_args &A = *args;
+    if (!(A.scale > 0.0) || !std::isfinite(A.scale)) return fail(h, BP_EINVAL, "bp_render: scale must be positive");
+    if (!std::isfinite(A.tx) || !std::isfinite(A.ty) || !std::isfinite(A.cx) || !std::isfinite(A.cy) || !std::isfinite(A.path_half_px))
+        return fail(h, BP_EINVAL, "bp_render: transform must be finite");
+    if (A.width <= 0 || A.height <= 0 || A.width > BP_RENDER_MAX_SIDE || A.height > BP_RENDER_MAX_SIDE ||
+        (long long)A.width * A.height > BP_RENDER_MAX_PIXELS)
+        return fail(h, BP_EINVAL, "bp_render: frame size outside 1..8192 per side / 2^24 pixels");
+    if (A.max_path < 0 || A.max_path > BP_RENDER_MAX_PATH || ((paths == nullptr) != (path_len == nullptr)) || (paths && A.max_path == 0))
+        return fail(h, BP_EINVAL, "bp_render: paths and path_len go together, with 1 <= max_path <= BP_RENDER_MAX_PATH");
+    if (!h->loaded || !h->was_reset) return fail(h, BP_ESTATE, "not reset");
+    if (!h->r_table) return fail(h, BP_ESTATE, "no render table (bp_set_render_table)");
+    BP_DEVICE(h);
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<int> ids(k);
+    HIPCHK(h, hipMemcpyAsync(ids.data(), env_ids, sizeof(int) * k, hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    for (int i = 0; i < k; i++)
+        if (ids[i] < 0 || ids[i] >= h->num_envs) return fail(h, BP_EINVAL, "bp_render: env id " + std::to_string(ids[i]) + " outside the batch");
+    RenderK K;
+    K.wv = h->D.wv; K.sc_nv = h->D.sc_nv; K.sc_prop = h->D.sc_prop; K.e_trial = h->D.e_trial; K.e_nb = h->D.e_nb;
+    const bool box = h->P.env_kind == BP_ENV_BOX;
+    K.alive = box ? h->Q.alive : nullptr; K.first_box = box ? h->B.first_box : 0; K.nbox = box ? h->B.nbox : 0;
+    K.nbcap = h->nbcap; K.num_envs = h->num_envs; K.num_trials = h->num_trials;
+    K.order = h->r_order; K.rgb = h->r_rgb; K.prims = h->r_prims; K.nslot = h->nbcap; K.nunder = h->r_nunder; K.nover = h->r_nover;
+    K.env_ids = env_ids; K.paths = paths; K.path_len = path_len; K.max_path = paths ? A.max_path : 0;
+    K.width = A.width; K.height = A.height;
+    K.tiles_x = (A.width + RENDER_TW - 1) / RENDER_TW;
+    K.tiles = K.tiles_x * ((A.height + RENDER_TH - 1) / RENDER_TH);
+    K.scale = A.scale; K.tx = A.tx; K.ty = A.ty; K.cx = A.cx; K.cy = A.cy; K.path_half = A.path_half_px;
+    K.background = A.background & 0xFFFFFFu; K.out = out;
+    const int chunk = std::max(1, (1 << 22) / K.tiles);    // frames per launch: at most 2^22 workgroups
+    for (int f0 = 0; f0 < k; f0 += chunk) {
+        K.frame0 = f0;
+        const int nf = std::min(chunk, k - f0);
+        hipLaunchKernelGGL(k_render, dim3((unsigned)(nf * K.tiles)), dim3(RENDER_THREADS), 0, st, K);
+        HIPCHK(h, hipGetLastError());
+    }
     return BP_OK;
 }
 

@@ -37,6 +37,9 @@ def _bd_cfg(cfg):
 class BatchedBoxDeliveryEnv(BatchedShipIceEnv):
     """E independent box-delivery environments on one GPU: reset(mask) / step(actions) with device tensors."""
 
+    render_task = "box_delivery"
+
+
     def __init__(self, num_envs, cfg=None, trials=None, device="cuda:0", env_id_offset=0, num_trials=32, seed=None, bd_overrides=None):
         if not torch.cuda.is_available():
             raise _lib.BpError("BatchedBoxDeliveryEnv needs a ROCm GPU (torch.cuda.is_available() is False); no CPU fallback")
@@ -197,7 +200,11 @@ class BoxDeliveryEnv(Env):
                 bool(self._b.truncated[0].item()), info)
 
     def render(self, mode="human", close=False):
-        raise NotImplementedError("rendering (pygame) is outside the accelerated path")
+        """rgb_array: the frame of this env with the controller's current waypoints as the path (numpy [H, W, 3]; benchpush_amd/render.py).
+        human: no window and no snapshot (the reference's save branch is disabled, box_delivery_env.py:1275): warns once, returns None."""
+        from ..render import adapter_render
+        _, wp, nwp = self._b.box_state()
+        return adapter_render(self, mode, wp[0, : int(nwp[0]), :2], None)
 
     def close(self):
         self._b.close()

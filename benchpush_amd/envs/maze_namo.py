@@ -48,6 +48,9 @@ def default_layouts(cfg, num_layouts, base_seed=0):
 class BatchedMazeEnv(BatchedShipIceEnv):
     """E independent maze-NAMO environments on one GPU (reset / step / world_polys / ... as BatchedShipIceEnv)."""
 
+    render_task = "maze"
+
+
     def __init__(self, num_envs, cfg=None, layouts=None, device="cuda:0", env_id_offset=0, num_layouts=64, base_seed=0):
         if not torch.cuda.is_available():
             raise _lib.BpError("BatchedMazeEnv needs a ROCm GPU (torch.cuda.is_available() is False); no CPU fallback")
@@ -194,7 +197,11 @@ class MazeNAMO(Env):
         self.path = new_path
 
     def render(self, mode="human", close=False):
-        raise NotImplementedError("rendering (pygame) is outside the accelerated path")
+        """rgb_array: the frame of this env with the path of update_path (numpy [H, W, 3]; benchpush_amd/render.py).  human: no window; with
+        cfg.render_snapshot every call writes <output_dir>/t<episode_idx>/<t>.png (maze_NAMO_env.py:604-606), otherwise warns once.  Returns None."""
+        from ..render import adapter_render, snapshot_path
+        snap = snapshot_path(self.cfg, self.episode_idx, self.t) if mode == "human" and self.cfg.get("render_snapshot", False) else None
+        return adapter_render(self, mode, self.path, snap)
 
     def close(self):
         self._b.close()

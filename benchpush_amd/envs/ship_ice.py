@@ -76,6 +76,8 @@ class BatchedShipIceEnv(_BatchedBase):
     Trial selection generalises ``episode_idx % len(experiment)`` (:188) to ``(global_env_id + episode_idx) % T``.
     """
 
+    render_task = "ship_ice"
+
     def __init__(self, num_envs, cfg=None, trials=None, device="cuda:0", env_id_offset=0, num_trials=100, base_seed=0):
         if not torch.cuda.is_available():
             raise _lib.BpError("BatchedShipIceEnv needs a ROCm GPU (torch.cuda.is_available() is False); no CPU fallback")
@@ -165,6 +167,65 @@ class BatchedShipIceEnv(_BatchedBase):
         cnt = torch.zeros((self.num_envs, self.nb_cap), dtype=torch.int32, device=self.device)
         _lib.check(self.L, self.h, self.L.bp_get_world_polys(self.h, _ptr(out), _ptr(cnt), self._stream()), "bp_get_world_polys")
         return out, cnt
+
+    # -- rgb_array frames (benchpush_amd/render.py states the frame) --------------------------------------
+    def render_table(self):
+        """The per-slot draw table (render.render_table) and the primitives (render.overlay_prims) this handle renders with."""
+        from .. import render as R
+        if getattr(self, "_rtable", None) is None:
+            task = R.task_of(self)
+            self._rtable = dict(R.render_table(task, self), prims=R.overlay_prims(task, self))
+        return self._rtable
+
+    def _upload_render_table(self):
+        if getattr(self, "_rtable_loaded", False):
+            return
+        from .. import render as R
+        t = self.render_table()
+        order = np.ascontiguousarray(t["order"], np.int32)
+        rgb = np.ascontiguousarray(t["rgb"][..., 0].astype(np.uint32) | (t["rgb"][..., 1].astype(np.uint32) << 8) | (t["rgb"][..., 2].astype(np.uint32) << 16))
+        prims = R.prim_array(t["prims"])
+        _lib.check(self.L, self.h, self.L.bp_set_render_table(self.h, order.shape[0], order.shape[1], order.ctypes.data_as(C.c_void_p),
+                                                             rgb.ctypes.data_as(C.c_void_p), len(t["prims"]), C.cast(prims, C.c_void_p)),
+                   "bp_set_render_table")
+        self._rtable_loaded = True
+
+    def frame_size(self, scale=None):
+        """(H, W) of this task's frames at `scale` (cfg.render_scale if None)."""
+        from .. import render as R
+        return R.frame_size(R.task_of(self), self.cfg, scale)
+
+    def render_frames(self, env_ids=None, scale=None, paths=None, out=None):
+        """rgb_array frames of the envs `env_ids` (None: all): device uint8 [k, H, W, 3] (render.py states the frame).  paths: None or a list of k
+        polylines (arrays [n, >= 2] of world points, or None), drawn as the planned path.  `out` may be a preallocated [k, H, W, 3] uint8 tensor."""
+        from .. import render as R
+        self._upload_render_table()
+        task = R.task_of(self)
+        if env_ids is None:
+            ids = torch.arange(self.num_envs, dtype=torch.int32, device=self.device)
+        else:
+            ids = torch.as_tensor(env_ids).reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
+        k = int(ids.numel())
+        pt = pl = None
+        max_path = 0
+        if paths is not None:
+            if len(paths) != k:
+                raise ValueError("paths must hold one polyline (or None) per env id")
+            pts = [np.zeros((0, 2)) if p is None or len(p) == 0 else np.asarray(p, np.float64).reshape(len(p), -1)[:, :2] for p in paths]
+            max_path = max(1, max(len(p) for p in pts))
+            host = np.zeros((k, max_path, 2), np.float64)
+            for i, p in enumerate(pts):
+                host[i, : len(p)] = p
+            pt = torch.from_numpy(host).to(self.device)
+            pl = torch.tensor([len(p) for p in pts], dtype=torch.int32, device=self.device)
+        args = R.render_args(task, self.cfg, scale, max_path)
+        if out is None:
+            out = torch.empty((max(k, 0), args.height, args.width, 3), dtype=torch.uint8, device=self.device)
+        elif tuple(out.shape) != (k, args.height, args.width, 3) or out.dtype != torch.uint8 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous uint8 tensor [%d, %d, %d, 3]" % (k, args.height, args.width))
+        _lib.check(self.L, self.h, self.L.bp_render(self.h, C.byref(args), _ptr(ids) if k else None, k, _ptr(pt), _ptr(pl), _ptr(out), self._stream()),
+                   "bp_render")
+        return out
 
     def body_state(self):
         out = torch.zeros((self.num_envs, self.nb_cap, 9), dtype=torch.float64, device=self.device)
@@ -433,7 +494,11 @@ class ShipIceEnv(Env):
         self.path = new_path
 
     def render(self, mode="human", close=False):
-        raise NotImplementedError("rendering (pygame) is outside the accelerated path")
+        """rgb_array: the frame of this env with the path of update_path (numpy [H, W, 3]; benchpush_amd/render.py).  human: no window; with
+        cfg.render_snapshot every call writes <output_dir>/t<episode_idx>/<t>.png (ship_ice_env.py:489-491), otherwise warns once.  Returns None."""
+        from ..render import adapter_render, snapshot_path
+        snap = snapshot_path(self.cfg, self.episode_idx, self.t) if mode == "human" and self.cfg.get("render_snapshot", False) else None
+        return adapter_render(self, mode, self.path, snap)
 
     def close(self):
         self._b.close()

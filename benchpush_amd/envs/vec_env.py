@@ -109,6 +109,8 @@ class BatchedVecEnv(_Base):
         self._host = None          # pinned host buffers of the to_numpy path, allocated on first use
         if _Base is not object:
             _Base.__init__(self, self.num_envs, self.observation_space, self.action_space)
+        self.render_mode = "rgb_array"
+        self.render_indices = list(range(min(self.num_envs, 16)))   # get_images() renders these envs (all 4096 ship-ice frames would be 9.4 GB)
 
     # -- host buffers of the numpy path: pinned, allocated once ------------------------------------------
     def _host_buffers(self):
@@ -196,6 +198,22 @@ class BatchedVecEnv(_Base):
                 self.env.check_errors()
             finally:
                 self.env.close()
+
+    # -- frames (benchpush_amd/render.py): VecVideoRecorder / RecordVideo read get_images() or render() -----------------------------
+    def get_images(self):
+        """rgb_array frames of the envs in ``render_indices``: a list of numpy uint8 [H, W, 3]."""
+        if not len(self.render_indices):
+            return []
+        frames = self.env.render_frames(list(self.render_indices)).cpu().numpy()
+        return [f for f in frames]
+
+    def render(self, mode="rgb_array"):
+        """The frames of ``get_images()`` tiled into one mosaic (render.tile_images); only mode "rgb_array" exists."""
+        if mode not in (None, "rgb_array"):
+            raise ValueError("BatchedVecEnv renders rgb_array frames only (no window backend), got mode %r" % (mode,))
+        from ..render import tile_images
+        imgs = self.get_images()
+        return tile_images(imgs) if imgs else None
 
     # minimal VecEnv plumbing used by SB3
     def seed(self, seed=None):

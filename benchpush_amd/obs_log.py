@@ -13,7 +13,7 @@ import zlib
 
 import numpy as np
 
-__all__ = ["write_gray_png", "read_gray_png", "dump_channels", "refuse_render_log_obs"]
+__all__ = ["write_gray_png", "read_gray_png", "write_rgb_png", "read_png", "dump_channels", "refuse_render_log_obs"]
 
 
 def _chunk(tag, data):
@@ -27,17 +27,37 @@ def write_gray_png(path, img):
         raise ValueError("write_gray_png wants a 2-D array, got shape %r" % (a.shape,))
     if a.dtype != np.uint8:
         a = (np.clip(a.astype(np.float64), 0.0, 1.0) * 255).astype(np.uint8)
-    h, w = a.shape
-    raw = np.empty((h, w + 1), np.uint8)
+    _write_png(path, a, 0)
+
+
+def write_rgb_png(path, img):
+    """8-bit RGB PNG (colour type 2) of a uint8 [H, W, 3] frame (render_frames / render(mode="rgb_array"))."""
+    a = np.ascontiguousarray(img)
+    if a.ndim != 3 or a.shape[2] != 3 or a.dtype != np.uint8:
+        raise ValueError("write_rgb_png wants a uint8 [H, W, 3] array, got %s %r" % (a.dtype, a.shape))
+    _write_png(path, a, 2)
+
+
+def _write_png(path, a, ctype):
+    """One IDAT of filter-0 scanlines: colour type 0 (grey, [H, W]) or 2 (RGB, [H, W, 3])."""
+    h, w = a.shape[:2]
+    raw = np.empty((h, a[0].size + 1), np.uint8)
     raw[:, 0] = 0                      # filter type 0 on every scanline
-    raw[:, 1:] = a
-    png = b"\x89PNG\r\n\x1a\n" + _chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 0, 0, 0, 0)) + _chunk(b"IDAT", zlib.compress(raw.tobytes(), 6)) + _chunk(b"IEND", b"")
+    raw[:, 1:] = a.reshape(h, -1)
+    png = b"\x89PNG\r\n\x1a\n" + _chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, ctype, 0, 0, 0)) + _chunk(b"IDAT", zlib.compress(raw.tobytes(), 6)) + _chunk(b"IEND", b"")
     with open(path, "wb") as f:
         f.write(png)
 
 
 def read_gray_png(path):
     """Inverse of `write_gray_png` (tests): uint8 [H, W]."""
+    a = read_png(path)
+    assert a.ndim == 2
+    return a
+
+
+def read_png(path):
+    """Inverse of `write_gray_png` / `write_rgb_png` (tests): uint8 [H, W] or [H, W, 3]."""
     b = open(path, "rb").read()
     assert b[:8] == b"\x89PNG\r\n\x1a\n"
     pos, idat, w = 8, b"", None
@@ -46,13 +66,15 @@ def read_gray_png(path):
         data = b[pos + 8: pos + 8 + n]
         if tag == b"IHDR":
             w, h, depth, ctype = struct.unpack(">IIBB", data[:10])
-            assert depth == 8 and ctype == 0
+            assert depth == 8 and ctype in (0, 2)
         elif tag == b"IDAT":
             idat += data
         pos += 12 + n
-    raw = np.frombuffer(zlib.decompress(idat), np.uint8).reshape(h, w + 1)
+    ch = 3 if ctype == 2 else 1
+    raw = np.frombuffer(zlib.decompress(idat), np.uint8).reshape(h, w * ch + 1)
     assert not raw[:, 0].any()
-    return raw[:, 1:].copy()
+    px = raw[:, 1:].copy()
+    return px.reshape(h, w, 3) if ch == 3 else px
 
 
 def dump_channels(output_dir, episode_idx, t, channels):

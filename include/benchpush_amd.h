@@ -359,6 +359,48 @@ int bp_bd_get_cycle_skips(bp_handle *h, uint32_t *out2_host);
 /* tests: per-env box bookkeeping, host buffers: alive uint8 [E][24], waypoints double [E][64][3], nwp int32 [E] (synchronises) */
 int bp_bd_get_state(bp_handle *h, uint8_t *alive, double *waypoints, int32_t *nwp);
 
+/* ---- rgb_array frames (benchpush/common/utils/renderer.py Renderer.render; benchpush_amd/render.py states the frame) ----
+ * A frame is uint8 [H][W][3], row 0 at the top.  World point (x, y) maps to the frame point
+ *   col = (x + tx) * scale + cx,   row = cy - (y + ty) * scale     (binary64, in this order)
+ * and pixel (r, c) is sampled at the point (col c, row r).  A polygon (3+ vertices) covers the pixels that skimage's point_in_polygon
+ * rule accepts; a capsule (segment a-b, half-width h) covers the pixels with dist2 <= h*h.  Painter's order, bottom first: the background,
+ * the primitives of layer 0, the shape slots in the table's order, the path segments of the frame's env, the primitives of layer 1. */
+#define BP_RENDER_MAX_PRIMS 256
+#define BP_RENDER_PRIM_VERTS 8
+#define BP_RENDER_MAX_SIDE 8192            /* frame width and height cap */
+#define BP_RENDER_MAX_PIXELS (1 << 24)     /* frame area cap (W * H) */
+#define BP_RENDER_MAX_PATH 4096            /* path points per env */
+typedef struct bp_render_prim {
+    int32_t kind;     /* 0: filled polygon of nv (3..8) world vertices; 1: capsule from v[0] to v[1] */
+    int32_t layer;    /* 0: under the shapes (box-delivery receptacle); 1: over the shapes and the paths (goal line, goal disc, clearance boundary) */
+    uint32_t rgb;     /* r | g << 8 | b << 16 */
+    int32_t nv;
+    double half_px;   /* capsule half-width = half_px + half_world * scale */
+    double half_world;
+    double v[BP_RENDER_PRIM_VERTS][2];
+} bp_render_prim;
+typedef struct bp_render_args {
+    double scale, tx, ty, cx, cy;    /* the transform above */
+    int32_t width, height;           /* frame size in pixels */
+    uint32_t background;             /* r | g << 8 | b << 16 */
+    int32_t max_path;                /* path points per env in `paths` (0: no paths) */
+    double path_half_px;             /* half-width of the path segments, in pixels */
+} bp_render_args;
+int32_t bp_sizeof_render_args(void);
+int32_t bp_sizeof_render_prim(void);
+/* Per-slot draw table, host buffers, copied at call time.  order int32 [T][nslot]: the slots of trial t bottom first, -1 = none (slots at or
+ * above the env's body count are skipped too); rgb uint32 [T][nslot] colour of slot s in trial t; prims [nprim] (nprim <= BP_RENDER_MAX_PRIMS).
+ * T must equal the handle's trial count and nslot its slot capacity (bp_nb_cap).  Slots with 2 vertices (maze walls) are capsules of
+ * half-width shape radius * scale; polygons ignore the shape radius.  Box-delivery / area-clearing: removed boxes are not drawn. */
+int bp_set_render_table(bp_handle *h, int32_t T, int32_t nslot, const int32_t *order, const uint32_t *rgb, int32_t nprim, const bp_render_prim *prims);
+/* k frames of the envs env_ids[0..k) (device int32 [k]) into out (device uint8 [k][H][W][3]; 64-bit offsets).  paths: device double
+ * [k][max_path][2] world points and path_len device int32 [k] (points used, clamped to max_path), or both null.  Reads the handle's state
+ * only and runs on `stream` after the work already queued there (a step's forked work joins back to the caller's stream).  BP_EINVAL for
+ * ids outside [0, E), k <= 0, scale <= 0 or a frame above the caps; BP_ESTATE before bp_set_render_table or bp_reset.  Synchronises
+ * `stream` once to check the ids. */
+int bp_render(bp_handle *h, const bp_render_args *args, const int32_t *env_ids, int32_t k, const double *paths, const int32_t *path_len,
+              uint8_t *out, void *stream);
+
 const char *bp_last_error(const bp_handle *h);
 int32_t bp_abi_version(void);
 int32_t bp_sizeof_config(void);   /* sizeof(bp_config), so a binding can verify its struct layout */
