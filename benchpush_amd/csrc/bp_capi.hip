@@ -138,6 +138,24 @@ static unsigned sched_yield_mask(bool solo_launch, int steps, int chunk)
     const int first = (2 * steps + 5 * chunk - 1) / (5 * chunk);   // ceil(0.4 * steps / chunk)
     return first >= 32 ? 0u : (0xFFFFFFFFu << first);
 }
+// Park images of the scheduler (bp_device.hpp: bp_img_bytes; image_store / image_load in bp_kernels.hpp): one per env, next to sq_carry / sq_moved.  An env that
+// yields inside a step is copied out and back verbatim -- LDS block, arbiter registers, sub-step state -- instead of going through the persistent format.
+// Bit-identical, and it halves the direct cost of a switch (park 5.4 -> 2.6 us, resume 12.9 -> 7.4 us, no cold first sub-step: profiles/sched_image/), but at ~3 switches
+// per env that is ~1 % of the slot-time and the launch followed by less than its run-to-run spread in the same-box A/B: measured-and-not-adopted, OFF by default, BP_SCHED_IMAGE=1 switches it on
+// (tools/experiments/README.md).  Pairing launches never use images (a parked env may be continued by a half-wave there).
+static int sched_image_setup(bp_handle *h)
+{
+    const int want = getenv("BP_SCHED_IMAGE") ? atoi(getenv("BP_SCHED_IMAGE")) : 0;
+    h->P.sq_image = 0; h->D.sq_img = nullptr;
+    if (!want || h->P.pair_mode == 2) return BP_OK;
+    h->P.sq_img_lds = (unsigned)h->sched_lds;
+    h->P.sq_img_stride = bp_img_bytes(h->P.sq_img_lds);
+    unsigned char *d_img;
+    int rc = dalloc(h, &d_img, (size_t)h->num_envs * h->P.sq_img_stride);
+    if (rc) return rc;
+    h->D.sq_img = d_img; h->P.sq_image = 1;
+    return BP_OK;
+}
 // ---- is this process alone on its device? --------------------------------------------------------------------------------------------------------
 // A resident kernel holds every wave slot until its launch is over: two PROCESSES that share one GPU can then only alternate by saving and restoring
 // 2 048 wavefronts (80 ms per launch measured in a two-rank rehearsal on one device).  One rank per GPU -- the deployment this library is
@@ -543,6 +561,7 @@ static int upload_trials(bp_handle *h, const std::vector<std::vector<bpgeom::Sha
             // (pairing launches have a resident kernel of their own, k_physics_step_schedr: the kernel that holds both step bodies INLINE lost 4 % at 8192 envs as a
             // resident loop -- 266 spilled VGPRs against 203)
             h->P.sq_ymask = sched_yield_mask(h->P.pair_mode != 2, h->P.steps, h->P.sq_chunk);
+            if ((rc = sched_image_setup(h))) return rc;
             if (h->P.pair_mode != 2 && h->P.sq_parts == 1) { int rc2 = sched_persist_setup(h); if (rc2) return rc2; }
             if (h->P.pair_mode == 2) {
                 HIPCHK(h, hipFuncSetAttribute((const void *)k_physics_step_schedr, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->sched_lds));
@@ -593,6 +612,7 @@ static int upload_trials(bp_handle *h, const std::vector<std::vector<bpgeom::Sha
             if (const char *ev2 = getenv("BP_SCHED_DEBUG_DROP")) h->P.sq_debug = atoi(ev2);
 #endif
             h->sched_lds = h->lds_bytes;
+            if ((rc = sched_image_setup(h))) return rc;
             HIPCHK(h, hipFuncSetAttribute((const void *)k_physics_step_sched_maze, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
             HIPCHK(h, hipFuncSetAttribute((const void *)k_physics_step_schedl_maze, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
             if ((rc = sched_persist_setup(h))) return rc;

@@ -41,6 +41,9 @@ struct DevParams {
     int sq_lrpt, sq_bw, sq_hyst;               // longest-remaining-first scheduling: on / row width in wave cycles >> 8 / rows a waiting env must be ahead by
     int sq_hold;                               // 1: envs of the top priority class do not yield to envs that have not started yet (BP_SCHED_HOLD)
     int sq_mode;                               // 0 = scheduled launch, 1 = completion launch: workgroup b finishes env b if the scheduled launch left it unfinished
+    int sq_image;                              // 1: an env parked inside a step leaves as a raw state image (the park image below) and is resumed from it; 0 (the default; BP_SCHED_IMAGE=1 switches images on): through store_state / load_state
+    unsigned sq_img_lds;                       // bytes of the env's LDS block that the image holds (the scheduler kernels' dynamic LDS); sq_img_stride: bytes of one env's image
+    unsigned sq_img_stride;
     int sq_debug;                              // test hook (BP_SCHED_DEBUG_DROP=1): env 1 is parked after its first chunk and never queued, the watchdog is short
     int dbg_paths;                             // test hook (BP_DEBUG_PATHS bit mask): 1 no candidate cache, 2 bound rounds through the sequential (flushing) loop,
                                                // 4 cached planes always through the support query, 8 manifold support vertices always through the support query
@@ -84,6 +87,7 @@ struct DevPtrs {
     int *sq_ctr;             // [16][SQ_MAXLEV + 2][2]: (head, tail) per level; row SQ_MAXLEV = (finished, total) of the XCD
     unsigned *sq_carry;      // [E][4] step-local state across chunks: yaw_violated, boundary_violated, work proxy, wave cycles >> 8
     unsigned char *sq_moved; // [E][nbcap] shape moved in an earlier chunk of this step
+    unsigned char *sq_img;   // [E][P.sq_img_stride] park images (bp_img_bytes below); null when P.sq_image == 0
     int *sq_done;            // [E] the env's step is complete (cleared by k_sched_init)
     int *sq_lev;             // [E] chunks completed when the env was last parked
     unsigned *sq_thr;        // [1] cost (256-cycle units) of the previous step's env at rank E / 256 from the top: k_make_order; 0xFFFFFFFF before the first step
@@ -221,7 +225,25 @@ __host__ __device__ inline LdsMap bp_lds_map(const int nbcap, const int mvcap, c
     return m;
 }
 
-#define SQ_MAXLEV 16
+// ---- park image of the preemptive step scheduler ---------------------------------------------------------------------------------------------
+// An env that yields at a chunk boundary is resumed later in the same launch by the same kernel with the same LDS map, so its running state is copied out
+// verbatim instead of being converted to the persistent format and re-derived: [the LDS block, rounded up to 1 KB][ArbReg, field-major: 20 rows of 64 doubles,
+// 10 rows of 64 words][one row of 64 words: SubState::err per lane][BpImgHdr: the wave-uniform rest of SubState and the step-locals, written by lane 0].  Every
+// store / load instruction of the wave is one contiguous row.  33 792 bytes per env with the 20 480-byte LDS block of the ship-ice kernels: 138 MB at 4096 envs.
+struct BpImgHdr {
+    unsigned stamp, stamp_start, costp, n_post, n_contact, n_first, ship_post, ship_contacts;
+    int nmv, nslots, nlevels, yaw_violated, boundary_violated, wall_flag, cc_ok, cc_kmax, quiescent, pad_;
+    unsigned long long prev_amask;
+    double curr_dt, total_ke, total_imp, ecoef_e, ecoef;
+};
+#define BP_IMG_DROWS 20   // ArbReg: rows of doubles
+#define BP_IMG_UROWS 11   // ArbReg: rows of words, + SubState::err
+#define BP_IMG_HDR 256
+static_assert(sizeof(BpImgHdr) <= BP_IMG_HDR, "park image header");
+__host__ __device__ inline unsigned bp_img_regs_off(const unsigned lds_bytes) { return (lds_bytes + 1023u) & ~1023u; }
+__host__ __device__ inline unsigned bp_img_bytes(const unsigned lds_bytes) { return bp_img_regs_off(lds_bytes) + 512u * BP_IMG_DROWS + 256u * BP_IMG_UROWS + BP_IMG_HDR; }
+
+#define SQ_MAXLEV 32   // queue rows per XCD and kind = chunks per step at most (one bit of DevParams::sq_ymask each): chunks of 13 sub-steps and up at 400 per step
 #define BP_DBL_MIN 2.2250738585072014e-308
 #define BP_PI 3.14159265358979323846
 #define BP_INF (__builtin_inf())

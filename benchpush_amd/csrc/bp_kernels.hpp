@@ -204,6 +204,67 @@ __device__ __forceinline__ void store_state(const DevParams &P, const DevPtrs &D
     }
 }
 
+// ---- park image (bp_device.hpp): the running state of an env, verbatim ---------------------------------------------------------------------------
+// Row r of a group of rows of T: lane l's element at base + (r * 64 + l) * sizeof(T) -- a wave-uniform base and a 32-bit lane offset, like gE.
+template <typename T> __device__ __forceinline__ T &img_at(unsigned char *const base, const unsigned row) { return *(T *)(base + (size_t)((row * 64u + (unsigned)lane_id()) * (unsigned)sizeof(T))); }
+#define BP_IMG_AROWS(X, A, S, db, ub) \
+    X(double, db, 0, A.jn0) X(double, db, 1, A.jt0) X(double, db, 2, A.jn1) X(double, db, 3, A.jt1) X(double, db, 4, A.n.x) X(double, db, 5, A.n.y) \
+    X(double, db, 6, A.r1_0.x) X(double, db, 7, A.r1_0.y) X(double, db, 8, A.r2_0.x) X(double, db, 9, A.r2_0.y) X(double, db, 10, A.r1_1.x) X(double, db, 11, A.r1_1.y) \
+    X(double, db, 12, A.r2_1.x) X(double, db, 13, A.r2_1.y) X(double, db, 14, A.ma) X(double, db, 15, A.ia) X(double, db, 16, A.mb) X(double, db, 17, A.ib) \
+    X(double, db, 18, A.e) X(double, db, 19, A.u) \
+    X(unsigned, ub, 0, A.key) X(unsigned, ub, 1, A.stamp) X(unsigned, ub, 2, A.h0) X(unsigned, ub, 3, A.h1) X(int, ub, 4, A.state) X(int, ub, 5, A.count) \
+    X(int, ub, 6, A.level) X(int, ub, 7, A.rank) X(int, ub, 8, A.slotA) X(int, ub, 9, A.slotB) X(int, ub, 10, S.err)
+__device__ __forceinline__ unsigned char *img_base(const DevParams &P, const DevPtrs &D, const int env) { return D.sq_img + (size_t)env * (size_t)P.sq_img_stride; }
+// park: the LDS block 16 bytes per lane and row, ArbReg field by field, the wave-uniform state from lane 0 (plain vector stores throughout)
+__device__ __forceinline__ void image_store(const DevParams &P, const DevPtrs &D, const ArbReg &A, const SubState &S, const int env, const unsigned stamp_start)
+{
+    const int lane = lane_id();
+    unsigned char *const img = img_base(P, D, env);
+    const unsigned char *const lds = (const unsigned char *)bp_smem;
+    for (unsigned off = (unsigned)lane * 16u; off < P.sq_img_lds; off += 1024u) *(uint4 *)(img + (size_t)off) = *(const uint4 *)(lds + off);
+    unsigned char *const db = img + bp_img_regs_off(P.sq_img_lds), *const ub = db + 512u * BP_IMG_DROWS;
+#define BP_IMG_ST(T, base, row, field) img_at<T>(base, row) = field;
+    BP_IMG_AROWS(BP_IMG_ST, A, S, db, ub)
+#undef BP_IMG_ST
+    if (lane == 0) {
+        BpImgHdr *const h = (BpImgHdr *)(ub + 256u * BP_IMG_UROWS);
+        h->stamp = S.stamp; h->stamp_start = stamp_start; h->costp = S.costp; h->n_post = S.n_post; h->n_contact = S.n_contact; h->n_first = S.n_first;
+        h->ship_post = S.ship_post; h->ship_contacts = S.ship_contacts; h->nmv = S.nmv; h->nslots = S.nslots; h->nlevels = S.nlevels;
+        h->yaw_violated = S.yaw_violated; h->boundary_violated = S.boundary_violated; h->wall_flag = S.wall_flag; h->cc_ok = S.cc_ok; h->cc_kmax = S.cc_kmax;
+        h->quiescent = S.quiescent; h->prev_amask = S.prev_amask; h->curr_dt = S.curr_dt; h->total_ke = S.total_ke; h->total_imp = S.total_imp;
+        h->ecoef_e = S.ecoef_e; h->ecoef = S.ecoef;
+    }
+}
+// resume: the inverse; returns the stamp the step began with.  The header is read through a wave-uniform address, so its values stay wave-uniform.
+__device__ __forceinline__ unsigned image_load(const DevParams &P, const DevPtrs &D, ArbReg &A, SubState &S, const int env)
+{
+    const int lane = lane_id();
+    unsigned char *const img = img_base(P, D, env);
+    unsigned char *const lds = (unsigned char *)bp_smem;
+    // the register rows first -- nothing waits for them before the first sub-step -- then the LDS block ten rows at a time: the loads of a batch are all in
+    // flight before the first of them is written to LDS
+    unsigned char *const db = img + bp_img_regs_off(P.sq_img_lds), *const ub = db + 512u * BP_IMG_DROWS;
+#define BP_IMG_LD(T, base, row, field) field = img_at<T>(base, row);
+    BP_IMG_AROWS(BP_IMG_LD, A, S, db, ub)
+#undef BP_IMG_LD
+    for (unsigned base = (unsigned)lane * 16u; base < P.sq_img_lds; base += 10u * 1024u) {
+        uint4 v[10];
+#pragma unroll
+        for (int k = 0; k < 10; k++) v[k] = *(const uint4 *)(img + (size_t)min(base + (unsigned)k * 1024u, P.sq_img_lds - 16u));   // (past the end: the last 16 bytes again, not written)
+#pragma unroll
+        for (int k = 0; k < 10; k++) { const unsigned off = base + (unsigned)k * 1024u; if (off < P.sq_img_lds) *(uint4 *)(lds + off) = v[k]; }
+    }
+    const BpImgHdr *const h = (const BpImgHdr *)(ub + 256u * BP_IMG_UROWS);
+    S.stamp = h->stamp; S.costp = h->costp; S.n_post = h->n_post; S.n_contact = h->n_contact; S.n_first = h->n_first;
+    S.ship_post = h->ship_post; S.ship_contacts = h->ship_contacts; S.nmv = h->nmv; S.nslots = h->nslots; S.nlevels = h->nlevels;
+    S.yaw_violated = h->yaw_violated; S.boundary_violated = h->boundary_violated; S.wall_flag = h->wall_flag; S.cc_ok = h->cc_ok; S.cc_kmax = h->cc_kmax;
+    S.quiescent = h->quiescent; S.prev_amask = h->prev_amask; S.curr_dt = h->curr_dt; S.total_ke = h->total_ke; S.total_imp = h->total_imp;
+    S.ecoef_e = h->ecoef_e; S.ecoef = h->ecoef;
+    const unsigned stamp_start = h->stamp_start;
+    __syncthreads();
+    return stamp_start;
+}
+
 // ---- queues of the preemptive step scheduler (k_physics_step_sched below) -----------------------------------------------------------------
 // D.sq_ctr: per XCD x SQ_MAXLEV + 2 rows of two ints: rows 0 .. SQ_MAXLEV-1 = (head, tail) of the queue of envs that have completed that many
 // chunks; row SQ_MAXLEV of XCD x = (envs waiting in any of x's queues, -); XCD 0 additionally keeps the launch-wide counters in row SQ_MAXLEV + 1 =
@@ -240,8 +301,13 @@ __device__ __forceinline__ int sq_pop_level(const DevParams &P, const DevPtrs &D
             // at load, a paired wave that yields mid-chunk; longest-remaining-first keys repeat too).  The popper TAKES the entry (exchange with -1),
             // the pusher waits for an empty one: entries of a row are interchangeable, so two poppers that meet on one slot a lap apart are harmless.
             int *slot = D.sq_items + ((size_t)xk * SQ_MAXLEV + l) * P.sq_cap + (int)((unsigned)h % (unsigned)P.sq_cap);
-            int e;
-            while ((e = atomicExch(slot, -1)) < 0) __builtin_amdgcn_s_sleep(1); // the pusher has taken the index, the id is on its way
+            int e, spin = 0;
+            while ((e = atomicExch(slot, -1)) < 0) { // the pusher has taken the index, the id is on its way
+                // ... unless the pusher gave up (sq_push: spin timeout after it had advanced the tail): same bound here, then every poller leaves and the
+                // completion launch finishes the parked envs -- a scheduler fault ends as its error code, not as a hang
+                if (++spin > (1 << 22)) { atomicOr(&D.e_err[0], BP_ERR_SCHED_TIMEOUT); if (atomicExch(sq_abort(D), 1) == 0) atomicAdd(&D.sq_warn[0], 1); return -1; }
+                __builtin_amdgcn_s_sleep(1);
+            }
             atomicSub(sq_waiting(D, xk), 1);
             return e;
         }
@@ -305,8 +371,9 @@ __device__ __forceinline__ bool sq_someone_behind(const DevParams &P, const DevP
 }
 // CHUNKED (k_physics_step_sched): the call resumes env `c_env`'s step after `c_lev` chunks of P.sq_chunk sub-steps and runs until the step is complete
 // (returns true) or, at a chunk boundary, an env that has completed fewer chunks is waiting in XCD c_x's queues (returns false, *c_lev_out = chunks
-// completed): an env that is behind everybody else -- a heavy one -- is never parked.  Parking goes through the same store / load as a step boundary,
-// the step-local flags through D.sq_carry.
+// completed): an env that is behind everybody else -- a heavy one -- is never parked.  A parked env leaves and returns as a raw image of its running state
+// (image_store / image_load); with P.sq_image == 0 and in pairing launches it goes through the same store / load as a step boundary, the step-local flags
+// through D.sq_carry.
 template <int mode, int KIND, bool CHUNKED = false, bool DAMP = false>
 __device__ __forceinline__ bool physics_body(const DevParams &P, const DevPtrs &D, const double *__restrict__ actions,
                                              const unsigned char *__restrict__ mask, double *__restrict__ reward,
@@ -364,6 +431,10 @@ __device__ __forceinline__ bool physics_body(const DevParams &P, const DevPtrs &
     const unsigned long long _t_kernel0 = __builtin_amdgcn_s_memtime();
 #endif
     init_regs(A, S);
+    // CHUNKED: an env that was parked inside this step comes back from its park image, and leaves as one (P.sq_image; pairing launches keep the persistent format:
+    // there a parked env may be continued by a half-wave, which has another LDS layout).  The first task of a step and its end go through load_state / store_state.
+    const bool img = CHUNKED && mode == MODE_STEP && P.sq_image != 0 && P.pair_mode != 2;
+    unsigned img_stamp_start = 0u;
     if (mode == MODE_RESET) {
         // ---- new space + bodies from the trial (ship_ice_env.py:109-216) ----
         for (int base = 0; base < nbcap; base += 64) {
@@ -438,6 +509,8 @@ __device__ __forceinline__ bool physics_body(const DevParams &P, const DevPtrs &
         A.slotA = A.slotB = 0;
         S.total_ke = 0.0; S.total_imp = 0.0; S.n_post = S.n_contact = S.n_first = 0;
         __syncthreads();
+    } else if (img && c_sub > 0) {
+        img_stamp_start = image_load(P, D, A, S, env);
     } else {
         load_state_a<KIND>(P, D, E, L, A, S, env);
         if (CHUNKED && c_sub > 0) {
@@ -460,7 +533,7 @@ __device__ __forceinline__ bool physics_body(const DevParams &P, const DevPtrs &
     const unsigned long long _tt_b = __builtin_amdgcn_s_memrealtime();
     unsigned long long _tt_c = 0ull;
 #endif
-    const unsigned stamp_start = S.stamp;
+    const unsigned stamp_start = (img && c_sub > 0) ? img_stamp_start : S.stamp;
     const unsigned costp_resume = S.costp;
     const int nsub = (mode == MODE_RESET) ? P.settle_steps : P.steps;
     const int it_first = CHUNKED ? c_sub : 0;
@@ -482,7 +555,7 @@ __device__ __forceinline__ bool physics_body(const DevParams &P, const DevPtrs &
     int c_it_parked = 0;
     bool step_done = true;
     int to_boundary = CHUNKED ? P.sq_chunk : 0x7FFFFFFF;   // sub-steps until the next chunk boundary
-    if (CHUNKED && c_sub == 0) { // nothing has moved in this step yet
+    if (CHUNKED && c_sub == 0 && !img) { // nothing has moved in this step yet (an image carries L.mvs and the step's first stamp instead)
         unsigned char *mvd_ = D.sq_moved + (size_t)env * nbcap;
         for (int i = lane; i < nbcap; i += 64) mvd_[i] = 0;
     }
@@ -557,6 +630,19 @@ __device__ __forceinline__ bool physics_body(const DevParams &P, const DevPtrs &
     const unsigned long long _tt_d = __builtin_amdgcn_s_memrealtime();
 #endif
     if (CHUNKED && !step_done) {
+        const int err_c = (ballot((S.err & BP_ERR_ADJ_OVERFLOW) != 0) ? BP_ERR_ADJ_OVERFLOW : 0) |
+                          (ballot((S.err & BP_ERR_ARB_OVERFLOW) != 0) ? BP_ERR_ARB_OVERFLOW : 0) |
+                          (ballot((S.err & BP_ERR_LEVEL_OVERFLOW) != 0) ? BP_ERR_LEVEL_OVERFLOW : 0);
+        if (img) {
+            // ---- end of a chunk: the env leaves as its park image; the queues and the rescue list read D.sq_sub / D.sq_lev, the end of the step the cycle count
+            image_store(P, D, A, S, env, stamp_start);
+            if (lane == 0) {
+                unsigned *cy = D.sq_carry + (size_t)env * 4;
+                cy[3] = (c_sub == 0 ? 0u : cy[3]) + (unsigned)((__builtin_amdgcn_s_memtime() - t_begin) >> 8);
+                D.sq_sub[env] = c_it_parked;
+                if (err_c) atomicOr(&D.e_err[env], err_c);
+            }
+        } else {
         // ---- end of a chunk: park the env exactly as at a step boundary; the step-local flags and the shapes that have moved so far go along
         unsigned char *mvd_ = D.sq_moved + (size_t)env * nbcap;
         for (int i = lane; i < E.nb; i += 64) if (L.mvs[i] > stamp_start) mvd_[i] = 1;
@@ -569,9 +655,6 @@ __device__ __forceinline__ bool physics_body(const DevParams &P, const DevPtrs &
             const unsigned rate = (S.costp - costp_resume) / (unsigned)max(c_it_parked - it_first, 1);
             *c_light_out = (keys <= P.pp_max_keys - 6 && S.nmv <= P.pp_max_mv / 2 && act <= P.pp_max_act && rate <= (unsigned)P.pp_rate) ? 1 : 0;
         }
-        const int err_c = (ballot((S.err & BP_ERR_ADJ_OVERFLOW) != 0) ? BP_ERR_ADJ_OVERFLOW : 0) |
-                          (ballot((S.err & BP_ERR_ARB_OVERFLOW) != 0) ? BP_ERR_ARB_OVERFLOW : 0) |
-                          (ballot((S.err & BP_ERR_LEVEL_OVERFLOW) != 0) ? BP_ERR_LEVEL_OVERFLOW : 0);
         if (lane == 0) {
             D.e_stamp[env] = S.stamp; D.e_currdt[env] = S.curr_dt;
             D.e_ke[env] = S.total_ke; D.e_imp[env] = S.total_imp;
@@ -581,6 +664,7 @@ __device__ __forceinline__ bool physics_body(const DevParams &P, const DevPtrs &
             cy[3] = (c_sub == 0 ? 0u : cy[3]) + (unsigned)((__builtin_amdgcn_s_memtime() - t_begin) >> 8);
             D.sq_sub[env] = c_it_parked;
             if (err_c) atomicOr(&D.e_err[env], err_c);
+        }
         }
 #ifdef BP_PROF
         if (D.prof != nullptr) { // a step that is run in several chunks accumulates (the tool clears the buffer before each step)
@@ -606,7 +690,7 @@ __device__ __forceinline__ bool physics_body(const DevParams &P, const DevPtrs &
         for (int base = 0; base < E.nb; base += 64) {
             const int i = base + lane;
             // shapes that did not move contribute exactly +0, so the test only saves work; across chunks the flag comes from D.sq_moved
-            const bool mvd = (i < E.nb) && ((L.mvs[i] > stamp_start) || (CHUNKED && c_sub > 0 && D.sq_moved[(size_t)env * nbcap + i] != 0)) &&
+            const bool mvd = (i < E.nb) && ((L.mvs[i] > stamp_start) || (CHUNKED && c_sub > 0 && !img && D.sq_moved[(size_t)env * nbcap + i] != 0)) &&
                              (kind_ctype(gE(E.kind, i)) == 2); // floes / boxes only
             double contrib = 0.0;
             if (mvd) {
@@ -785,7 +869,12 @@ __global__ __launch_bounds__(64, 2) void k_physics_step_pair(const DevParams P, 
 __global__ void k_sched_init(const DevParams P, const DevPtrs D)
 {
     const int tid = blockIdx.x * blockDim.x + threadIdx.x, nthr = gridDim.x * blockDim.x;
-    for (int i = tid; i < SQ_NX * SQ_MAXLEV * P.sq_cap; i += nthr) D.sq_items[i] = -1;
+    // (only the rows a launch can use: P.sq_levels of the SQ_MAXLEV per XCD and kind, all of them with longest-remaining-first keys)
+    const int nrows = P.sq_lrpt ? SQ_MAXLEV : P.sq_levels;
+    for (int i = tid; i < SQ_NX * nrows * P.sq_cap; i += nthr) {
+        const int xk = i / (nrows * P.sq_cap), r = i - xk * (nrows * P.sq_cap);
+        D.sq_items[(size_t)xk * SQ_MAXLEV * P.sq_cap + r] = -1;
+    }
     for (int i = tid; i < SQ_NX * (SQ_MAXLEV + 2) * 2; i += nthr) D.sq_ctr[i] = 0;
     for (int i = tid; i < P.num_envs; i += nthr) { D.sq_done[i] = 0; D.sq_lev[i] = 0; D.sq_sub[i] = 0; }
 }
