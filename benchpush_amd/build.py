@@ -61,6 +61,27 @@ def build_debug_paths(force=False, verbose=False):
     return DBG_LIB_PATH
 
 
+PROF_LIB_PATH = os.path.join(_HERE, "libbenchpush_hip_prof.so")
+
+
+def build_prof(force=False, verbose=False):
+    """Diagnostic twin with the in-kernel phase timers and trip counters (-DBP_PROF; loaded by BP_PROF=1, read through bp_debug_prof): tools/prof_phases.py
+    and the tests that must see which solver path a sub-step took (tests/test_gpu_bias_lanes.py)."""
+    if not force and os.path.exists(PROF_LIB_PATH):
+        t = os.path.getmtime(PROF_LIB_PATH)
+        if all(os.path.getmtime(p) <= t for p in [os.path.join(CSRC, f) for f in SOURCES] + _headers() if os.path.exists(p)):
+            return PROF_LIB_PATH
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    if not os.path.exists(hipcc):
+        hipcc = "hipcc"
+    cmd = [hipcc] + HIPCC_FLAGS + ["-DBP_PROF=1", "-o", PROF_LIB_PATH] + [os.path.join(CSRC, s) for s in SOURCES]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd, cwd=CSRC)
+    return PROF_LIB_PATH
+
+
 if __name__ == "__main__":
     print(build_hip(force=True, verbose=True))
     print(build_debug_paths(force=True, verbose=True))
+    print(build_prof(force=True, verbose=True))

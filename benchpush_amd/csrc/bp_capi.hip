@@ -265,6 +265,7 @@ int bp_create(const bp_config *cfg, int32_t num_envs, int64_t env_id_offset, int
     P.dt_sub = cfg->dt / cfg->steps;
     P.steps = cfg->steps; P.iterations = cfg->iterations; P.persistence = cfg->persistence; P.settle_steps = cfg->settle_steps;
     if (const char *evp = getenv("BP_DEBUG_PATHS")) P.dbg_paths = atoi(evp); // test hook: force the rarely taken paths of the narrow phase (bp_device.hpp)
+    P.bias_lanes = getenv("BP_BIAS_LANES") ? (atoi(getenv("BP_BIAS_LANES")) != 0) : 1;   // 0: sub-steps with a bias term take the bias copy of the solver passes
     P.damping_pow = cfg->damping_pow; P.bias_coef = cfg->bias_coef; P.slop = cfg->slop;
     P.target_speed = cfg->target_speed; P.max_yaw_rate = cfg->max_yaw_rate;
     P.map_w = cfg->map_w; P.map_h = cfg->map_h; P.goal_y = cfg->goal_y; P.m_to_pix = cfg->m_to_pix;
@@ -1332,6 +1333,7 @@ int bp_bd_create(const bp_bd_config *cfg, int32_t num_envs, int64_t env_id_offse
     P.dt_sub = cfg->ctrl_dt / cfg->steps;
     P.steps = cfg->steps; P.iterations = cfg->iterations; P.persistence = cfg->persistence; P.settle_steps = cfg->settle_steps;
     if (const char *evp = getenv("BP_DEBUG_PATHS")) P.dbg_paths = atoi(evp); // test hook: force the rarely taken paths of the narrow phase (bp_device.hpp)
+    P.bias_lanes = getenv("BP_BIAS_LANES") ? (atoi(getenv("BP_BIAS_LANES")) != 0) : 1;   // 0: sub-steps with a bias term take the bias copy of the solver passes
     P.damping_pow = cfg->damping_pow; P.bias_coef = cfg->bias_coef; P.slop = cfg->slop;
     P.target_speed = cfg->target_speed;
     P.skin = 0.25;

@@ -45,6 +45,7 @@ struct DevParams {
     unsigned sq_img_lds;                       // bytes of the env's LDS block that the image holds (the scheduler kernels' dynamic LDS); sq_img_stride: bytes of one env's image
     unsigned sq_img_stride;
     int sq_debug;                              // test hook (BP_SCHED_DEBUG_DROP=1): env 1 is parked after its first chunk and never queued, the watchdog is short
+    int bias_lanes;                            // 1 (default; BP_BIAS_LANES=0 switches it off): sub-steps with a bias term solve the bias system in mirror lanes of the no-bias passes (substep, 6d)
     int dbg_paths;                             // test hook (BP_DEBUG_PATHS bit mask): 1 no candidate cache, 2 bound rounds through the sequential (flushing) loop,
                                                // 4 cached planes always through the support query, 8 manifold support vertices always through the support query
     // two environments per wavefront (bp_physics_pair.hpp): 0 off, 1 fixed pairs (2b, 2b + 1) for the whole step (k_physics_step_pair: parity tests),
@@ -341,6 +342,11 @@ __device__ __forceinline__ double half_min(double v)
 __device__ __forceinline__ double readlane_f64(double v, int l)
 {
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
+}
+// every lane receives the double of the lane whose byte index (lane << 2) it passes; uniform call: ds_bpermute reads active lanes only
+__device__ __forceinline__ double bperm_f64(int lane4, double v)
+{
+    return __hiloint2double(__builtin_amdgcn_ds_bpermute(lane4, __double2hiint(v)), __builtin_amdgcn_ds_bpermute(lane4, __double2loint(v)));
 }
 __device__ __forceinline__ void halves_max_f64(double v, double &lo, double &hi)
 {

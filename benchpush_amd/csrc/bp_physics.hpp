@@ -1161,21 +1161,84 @@ __device__ __forceinline__ void substep(const DevParams &P, const EnvCtx &E, con
     // being predicated away -- two EXEC-mask branches less per pass (+2.8 % env-steps/s, same-box A/B).  Not for box-delivery, whose
     // kernel sits at the 256-VGPR limit of two waves per SIMD.
     constexpr bool SCRATCH_WB = (KIND != BP_ENV_BOX);
+    // ---- mirror lanes: the bias system of a warm arbiter rides in a free lane of the no-bias passes ------------------------------------------------
+    // Inside the solver the bias system (L.sb, L.sw[].y, jBias, bias, nMass) and the velocity system (L.sv, L.sw[].x, jn, jt, bounce, nMass, tMass) never
+    // read each other's values: they meet again in the next sub-step's position integrate.  The bias system is the same Gauss-Seidel sweep in the same colour
+    // order, and one contact of it is the normal-impulse part of one contact of the velocity system:
+    //     vbn = dot((vbb + perp(r2) * wbb) - (vba + perp(r1) * wba), n)          the expression of vrn, on the bias velocities
+    //     jBias = fmax(jbOld + (bias - vbn) * nMass, 0)                           jnAcc = fmax(jnOld + -(bounce + vrn) * nMass, 0) with bounce' = -bias:
+    //                                                                             -((-bias) + vbn) is the correctly rounded bias - vbn with its sign flipped
+    //                                                                             twice, i.e. the same double unless it is a zero (then the zeros may differ)
+    //     vba += (-(n * djb)) * ma, wba += ia * cross(r1, -(n * djb)), ...        apply_contact_impulses with j = vrotate(n, (djn, djt)), djt a zero
+    // So in a sub-step with a bias term every warm arbiter gets a mirror lane among the lanes whose key is ARB_FREE_KEY (their arbiter registers hold nothing
+    // live: cpSpaceArbiterSetFilter / the hand-over write every field before it is read).  The mirror receives the arbiter's geometry, masses, nMass, colour
+    // and slots through ds_bpermute, once per sub-step, and is set up with bounce' = -bias, tMass' = 0, friction' = 0, jn' = jt' = +0 (jBias is +0 after the
+    // prestep); its gather / scatter addresses point at L.sb[slot] and at the .y half of L.sw[slot].  The wave then runs the NO-bias copy of the passes over
+    // (warm arbiters + mirrors) -- the same instruction stream as a sub-step without bias terms, the single-colour register path included -- and the bias copy
+    // stays out of the hot loop.  Mirrors add |djn| to chg, so the fixed-point exit falls on the same iteration.  Nothing is copied back: the bias velocities
+    // are in the slots, jBias is dead after the solve, and the mirror's key stayed ARB_FREE_KEY throughout.
+    // Zeros: tMass' = 0 makes jt a zero (vrt is finite), jtMax' = 0 clamps it to a zero, djt is a zero; jnOld + jn with jnOld >= +0 never is -0 (a sum is
+    // -0 only if both terms are), so fmax(., 0) returns what the oracle's does even where -((-bias) + vbn) and bias - vbn are zeros of opposite sign.
+    // vrotate(n, (djn, +-0)) = (n.x * djn - +-0, +-0 + n.y * djn) equals n * djn except, possibly, in the sign of a component that is an exact zero; such a zero
+    // reaches the state only as an addend x + (+-0) * m or x + i * (a zero), which is x for every x but -0.  Bias velocities are never -0: every slot's sb and
+    // sw.y start as +0 (slot_get, the integrate phase, reset), the solver only ever stores sums to them, and a sum is -0 only if both terms are -0 (round to
+    // nearest).  A kinematic body's bias velocity is never stored at all (scratch slot) and stays the +0 it was loaded as; the register path's -0 guard reads
+    // whatever the lane gathers, so it covers the mirrors' infinite-mass sides as well.
+    // Fallback (the bias copy below): fewer free lanes than warm arbiters, P.bias_lanes == 0 (BP_BIAS_LANES=0), box-delivery (at the 256-VGPR line).
+    constexpr bool MIRRORS = (KIND != BP_ENV_BOX);
+    bool solve = warm;                 // lanes that run the colour passes: warm arbiters and their mirrors
+    bool mirrored = false;             // wave-uniform: this sub-step's bias system runs in mirror lanes
+    bool mir = false;
+    if (MIRRORS && any_bias) {
+        PROF_CNT(45, 1)
+        const unsigned long long fmask = ballot(A.key == ARB_FREE_KEY);
+        const int nw = __popcll(wmask);
+        if (P.bias_lanes != 0 && __popcll(fmask) >= nw) {
+            PROF_CNT(46, 1)
+            PROF_CNT(48, (lvlmask & (lvlmask - 1u)) != 0u ? 1 : 0)
+            mirrored = true;
+            // the r-th free lane mirrors the r-th warm lane (L.owner is scratch between the warm-set closure and the next sub-step)
+            if (warm) L.owner[popc_below(wmask, lane)] = (unsigned short)lane;
+            lds_sync();
+            const int fr = popc_below(fmask, lane);
+            mir = (A.key == ARB_FREE_KEY) && fr < nw;
+            const int src4 = (mir ? (int)L.owner[fr] : lane) << 2;
+            lds_sync();
+            auto take = [&](double &f) { const double t = bperm_f64(src4, f); if (mir) f = t; };
+            take(A.n.x); take(A.n.y);
+            take(A.r1_0.x); take(A.r1_0.y); take(A.r2_0.x); take(A.r2_0.y);
+            take(A.r1_1.x); take(A.r1_1.y); take(A.r2_1.x); take(A.r2_1.y);
+            take(A.ma); take(A.ia); take(A.mb); take(A.ib);
+            take(nMass0); take(nMass1);
+            const double b0 = bperm_f64(src4, bias0), b1 = bperm_f64(src4, bias1);
+            const int packed = __builtin_amdgcn_ds_bpermute(src4, A.count | (A.level << 8) | (A.slotA << 16) | (A.slotB << 24));
+            if (mir) {
+                A.count = packed & 0xFF; A.level = (packed >> 8) & 0xFF; A.slotA = (packed >> 16) & 0xFF; A.slotB = (packed >> 24) & 0xFF;
+                bounce0 = -b0; bounce1 = -b1; tMass0 = 0.0; tMass1 = 0.0;
+                A.jn0 = A.jt0 = A.jn1 = A.jt1 = 0.0; A.u = 0.0;
+            }
+            solve = warm || mir;
+        } else { PROF_CNT(47, 1) }
+    }
+    // gather / write-back addresses of the lane's two bodies in the no-bias passes: velocity and angular velocity of an arbiter, their bias twins of a mirror
+    d2 *const gvA = (mir ? L.sb : L.sv) + A.slotA, *const gvB = (mir ? L.sb : L.sv) + A.slotB;
+    double *const gwA = &L.sw[A.slotA].x + (mir ? 1 : 0), *const gwB = &L.sw[A.slotB].x + (mir ? 1 : 0);
     const int wA = (!SCRATCH_WB || A.ma != 0.0) ? A.slotA : BP_NSLOT, wB = (!SCRATCH_WB || A.mb != 0.0) ? A.slotB : BP_NSLOT;
+    d2 *const svA = (mir ? L.sb : L.sv) + wA, *const svB = (mir ? L.sb : L.sv) + wB;
+    double *const swA = &L.sw[wA].x + (mir ? 1 : 0), *const swB = &L.sw[wB].x + (mir ? 1 : 0);
     auto iterate = [&](auto bias_tag) {
     constexpr bool AB = decltype(bias_tag)::value;
     // the three parts of a colour pass for the lane's arbiter: velocities of its two bodies from their slots, cpArbiterApplyImpulse for its one or two contacts,
     // velocities back to the slots (an infinite-mass body's to the scratch slot)
     auto gather = [&](d2 &va, d2 &vb, d2 &wa2, d2 &wb2, d2 &vba, d2 &vbb) {
-        va = L.sv[A.slotA]; vb = L.sv[A.slotB];
         wa2 = mk2(0.0, 0.0); wb2 = mk2(0.0, 0.0); vba = mk2(0.0, 0.0); vbb = mk2(0.0, 0.0);
-        if (AB) { wa2 = L.sw[A.slotA]; wb2 = L.sw[A.slotB]; vba = L.sb[A.slotA]; vbb = L.sb[A.slotB]; }
-        else { wa2.x = L.sw[A.slotA].x; wb2.x = L.sw[A.slotB].x; }   // without bias terms only the angular velocity itself is read and written back: 8-byte LDS accesses
+        if (AB) { va = L.sv[A.slotA]; vb = L.sv[A.slotB]; wa2 = L.sw[A.slotA]; wb2 = L.sw[A.slotB]; vba = L.sb[A.slotA]; vbb = L.sb[A.slotB]; }
+        else { va = *gvA; vb = *gvB; wa2.x = *gwA; wb2.x = *gwB; }   // without bias terms only the angular velocity itself is read and written back: 8-byte LDS accesses
     };
     auto scatter = [&](const d2 va, const d2 vb, const d2 wa2, const d2 wb2, const d2 vba, const d2 vbb) {
         if (SCRATCH_WB) {
-            L.sv[wA] = va; if (AB) { L.sw[wA] = wa2; L.sb[wA] = vba; } else L.sw[wA].x = wa2.x;
-            L.sv[wB] = vb; if (AB) { L.sw[wB] = wb2; L.sb[wB] = vbb; } else L.sw[wB].x = wb2.x;
+            if (AB) { L.sv[wA] = va; L.sw[wA] = wa2; L.sb[wA] = vba; } else { *svA = va; *swA = wa2.x; }
+            if (AB) { L.sv[wB] = vb; L.sw[wB] = wb2; L.sb[wB] = vbb; } else { *svB = vb; *swB = wb2.x; }
         } else {
             if (A.ma != 0.0) { L.sv[A.slotA] = va; if (AB) { L.sw[A.slotA] = wa2; L.sb[A.slotA] = vba; } else L.sw[A.slotA].x = wa2.x; }
             if (A.mb != 0.0) { L.sv[A.slotB] = vb; if (AB) { L.sw[A.slotB] = wb2; L.sb[A.slotB] = vbb; } else L.sw[A.slotB].x = wb2.x; }
@@ -1241,20 +1304,20 @@ __device__ __forceinline__ void substep(const DevParams &P, const EnvCtx &E, con
     // (no-bias copy only, and not in the box-delivery instantiation: the extra live registers of the other copies push those kernels over the 256-VGPR line)
     if (!AB && KIND != BP_ENV_BOX && (lvlmask & (lvlmask - 1u)) == 0u && lvlmask != 0u) {
         d2 va = mk2(0.0, 0.0), vb = va, wa2 = va, wb2 = va, vba = va, vbb = va;
-        if (warm) gather(va, vb, wa2, wb2, vba, vbb);
+        if (solve) gather(va, vb, wa2, wb2, vba, vbb);
         auto negzero = [](double x) { return (((unsigned)__double2hiint(x) ^ 0x80000000u) | (unsigned)__double2loint(x)) == 0u; };
         bool nz = false;
-        if (warm && A.ma == 0.0) nz = negzero(va.x) || negzero(va.y) || negzero(wa2.x) || (AB && (negzero(wa2.y) || negzero(vba.x) || negzero(vba.y)));
-        if (warm && A.mb == 0.0) nz = nz || negzero(vb.x) || negzero(vb.y) || negzero(wb2.x) || (AB && (negzero(wb2.y) || negzero(vbb.x) || negzero(vbb.y)));
+        if (solve && A.ma == 0.0) nz = negzero(va.x) || negzero(va.y) || negzero(wa2.x) || (AB && (negzero(wa2.y) || negzero(vba.x) || negzero(vba.y)));
+        if (solve && A.mb == 0.0) nz = nz || negzero(vb.x) || negzero(vb.y) || negzero(wb2.x) || (AB && (negzero(wb2.y) || negzero(vbb.x) || negzero(vbb.y)));
         if (!ballot(nz)) {
             for (int it = 0; it < P.iterations; it++) {
                 PROF_CNT(42, 1)
                 PROF_CNT(43, 1)
                 double chg = 0.0;
-                if (warm) contacts(va, vb, wa2, wb2, vba, vbb, chg);
-                if (BP_UNLIKELY2(!ballot(warm && chg != 0.0))) break;
+                if (solve) contacts(va, vb, wa2, wb2, vba, vbb, chg);
+                if (BP_UNLIKELY2(!ballot(solve && chg != 0.0))) break;
             }
-            if (warm) scatter(va, vb, wa2, wb2, vba, vbb);
+            if (solve) scatter(va, vb, wa2, wb2, vba, vbb);
             lds_sync();
             return;
         }
@@ -1265,8 +1328,8 @@ __device__ __forceinline__ void substep(const DevParams &P, const EnvCtx &E, con
         for (unsigned lm = lvlmask; lm; lm &= lm - 1u) { // colours that hold a warm arbiter, ascending
             const int lvl = __ffs((int)lm) - 1;
             PROF_CNT(43, 1)
-            PROF_CNT(44, ballot(warm && A.level == lvl && A.count > 1) ? 1 : 0)
-            if (warm && A.level == lvl) {
+            PROF_CNT(44, ballot(solve && A.level == lvl && A.count > 1) ? 1 : 0)
+            if (solve && A.level == lvl) {
                 d2 va, vb, wa2, wb2, vba, vbb;
                 gather(va, vb, wa2, wb2, vba, vbb);
                 contacts(va, vb, wa2, wb2, vba, vbb, chg);
@@ -1276,10 +1339,10 @@ __device__ __forceinline__ void substep(const DevParams &P, const EnvCtx &E, con
         }
         // an iteration that changed no accumulated impulse applied only zero impulses: the state is a fixed point and
         // the remaining iterations would repeat it exactly
-        if (BP_UNLIKELY2(!ballot(warm && chg != 0.0))) break;
+        if (BP_UNLIKELY2(!ballot(solve && chg != 0.0))) break;
     }
     };
-    if (any_bias) iterate(std::true_type{}); else iterate(std::false_type{});
+    if (any_bias && !mirrored) iterate(std::true_type{}); else iterate(std::false_type{});
     PROF_ACC(8)
     // ---- 7. post-solve bookkeeping for ship(0) x floe arbiters, ascending key order ------------------------------
     {
