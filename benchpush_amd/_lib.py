@@ -27,7 +27,9 @@ EXPORTS = ["bp_abi_version", "bp_create", "bp_destroy", "bp_load_scenarios", "bp
            "bp_get_episode_metrics", "bp_get_episode_history", "bp_start_uniform", "bp_debug_round2", "bp_debug_scramble_hints",
            "bp_copy_rows_masked", "bp_pair_mode", "bp_get_pair_stats", "bp_bd_get_stragglers",
            "bp_device_shared", "bp_launch_policy_query", "bp_bd_budget", "bp_get_cost_stats", "bp_bd_get_cycle_skips",
-           "bp_sizeof_render_args", "bp_sizeof_render_prim", "bp_set_render_table", "bp_render"]
+           "bp_sizeof_render_args", "bp_sizeof_render_prim", "bp_set_render_table", "bp_render",
+           "bp_state_bytes", "bp_state_layout_id", "bp_save_state", "bp_load_state", "bp_clone_state", "bp_state_layout_query"]
+STATE_TRUSTED = 1    # BP_STATE_TRUSTED: bp_load_state / bp_clone_state skip the argument checks and the synchronisation
 
 
 class BpCostmapConfig(C.Structure):
@@ -173,8 +175,32 @@ def load():
             raise BpError("bp_render_args / bp_render_prim layout mismatch between benchpush_amd.render and the library")
         L.bp_set_render_table.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp]
         L.bp_render.argtypes = [vp, C.POINTER(RenderArgs), vp, C.c_int32, vp, vp, vp, vp]
+    if hasattr(L, "bp_save_state"):   # state records (absent from older builds loaded for same-box comparisons)
+        L.bp_state_bytes.argtypes = [vp]
+        L.bp_state_bytes.restype = C.c_int64
+        L.bp_state_layout_id.argtypes = [vp]
+        L.bp_state_layout_id.restype = C.c_uint64
+        L.bp_save_state.argtypes = [vp, vp, C.c_int32, vp, vp]
+        L.bp_load_state.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, vp]
+        L.bp_clone_state.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, vp]
+        L.bp_state_layout_query.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_uint64)]
     _lib = L
     return L
+
+
+def state_layout(env_kind, nbcap, task=0, map_cells=0):
+    """The state-record layout as a pure function of the shapes (bp_state_layout_query; no GPU, no handle): dict of offsets / bytes / widths per segment
+    (segment 0 is the header), the record size and the structural part of the layout id."""
+    import numpy as np
+    L = load()
+    n = L.bp_state_layout_query(int(env_kind), int(task), int(nbcap), int(map_cells), 0, None, None, None, None, None)
+    if n < 0:
+        raise BpError("bp_state_layout_query failed: %s (%d)" % (ERRORS.get(n, "?"), n))
+    off, nbytes, width = np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n, np.int32)
+    total, sid = C.c_int64(), C.c_uint64()
+    p = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+    L.bp_state_layout_query(int(env_kind), int(task), int(nbcap), int(map_cells), n, p(off), p(nbytes), p(width), C.byref(total), C.byref(sid))
+    return {"offsets": off, "bytes": nbytes, "widths": width, "total": int(total.value), "structure_id": int(sid.value)}
 
 
 def check(L, h, rc, what):

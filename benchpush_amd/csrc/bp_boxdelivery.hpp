@@ -52,26 +52,26 @@ struct BdPtrs {
     const d2 *recept_poly;          // [M][4] receptacle world vertices (hull order) + planes
     const d2 *recept_n;             // [M][4]
     const unsigned char *robot_chan;// [local_px*local_px] robot_state_channel * 255
-    // per env
-    unsigned char *alive;           // [E][BD_MAXBOX]
-    unsigned char *order;           // [E][BD_MAXBOX] self.boxes list order
-    int *nalive, *nprev;            // [E]
-    double *boxdist;                // [E][BD_MAXBOX]
-    d2 *boxpos;                     // [E][BD_MAXBOX] box position the cached distance was computed for
-    d2 *prev;                       // [E][BD_MAXBOX][4] prev_boxes by list position
-    double *cum;                    // [E][4] cumulative_distance, cumulative_reward, -, -
-    int *cnt;                       // [E][4] inactivity, cumulative_boxes, -, -
-    double *wp;                     // [E][BD_MAXWP][3]
-    int *nwp;                       // [E]
-    double *stepf;                  // [E][8] robot_distance, ix, iy, ih, hit, substeps, -, -
-    unsigned char *unfin;           // [E] 1 = the env's sim-step loop hit the budget of pass 0 (its loop state is in rs_i / rs_d) -- written by pass 0 for every env
+    // per env -- state records (bp_state.hpp: bp_state_layout): [record] = saved / restored / cloned with the env, [no record: why] otherwise
+    unsigned char *alive;           // [E][BD_MAXBOX]  [record]
+    unsigned char *order;           // [E][BD_MAXBOX] self.boxes list order  [record]
+    int *nalive, *nprev;            // [E]  [record]
+    double *boxdist;                // [E][BD_MAXBOX]  [record]
+    d2 *boxpos;                     // [E][BD_MAXBOX] box position the cached distance was computed for  [record]
+    d2 *prev;                       // [E][BD_MAXBOX][4] prev_boxes by list position  [record]
+    double *cum;                    // [E][4] cumulative_distance, cumulative_reward, -, -  [record]
+    int *cnt;                       // [E][4] inactivity, cumulative_boxes, -, -  [record]
+    double *wp;                     // [E][BD_MAXWP][3]  [record]
+    int *nwp;                       // [E]  [record]
+    double *stepf;                  // [E][8] robot_distance, ix, iy, ih, hit, substeps, -, -  [record]
+    unsigned char *unfin;           // [E] 1 = the env's sim-step loop hit the budget of pass 0 (its loop state is in rs_i / rs_d) -- written by pass 0 for every env  [no record: loop state of the two-pass step, as rs_i / rs_d]
     int *rs_i;                      // [E][16] phase, wi, path0, done_turning, dp_valid, sp_one, sim_steps, kcount, have_prev, still_done, total_sub, robot_hit, cycles >> 8
     double *rs_d;                   // [E][4 + 2 * 64] the controller's doubles (L.ctl) and the until-still loop's previous positions (one d2 per lane)
-    unsigned *straggler;            // [4] cumulative: envs resumed by pass 1, envs whose loops ran into STEP_LIMIT, recurrences found in execute_robot_path, sim steps they skipped
-    float *dist;                    // [E][SH*SW] spfa scratch
-    float *rmap;                    // [E][SH*SW] spfa map from the robot (observation channel 2)
+    unsigned *straggler;            // [4] cumulative: envs resumed by pass 1, envs whose loops ran into STEP_LIMIT, recurrences found in execute_robot_path, sim steps they skipped  [no record: counters of the handle]
+    float *dist;                    // [E][SH*SW] spfa scratch  [no record: rewritten before it is read]
+    float *rmap;                    // [E][SH*SW] spfa map from the robot (observation channel 2)  [record: bp_observe reads it]
     const d2 *goals;                // [ngoal] area-clearing goal points
-    unsigned char *cleared;         // [E][BD_MAXBOX] area-clearing box_clearance_statuses
+    unsigned char *cleared;         // [E][BD_MAXBOX] area-clearing box_clearance_statuses  [record]
 };
 
 // ---- deterministic libm replacements (fdlibm s_atan.c / e_atan2.c restated, fixed operation order, no FMA contraction) --------

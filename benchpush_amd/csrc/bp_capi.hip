@@ -20,6 +20,7 @@
 #include "bp_boxdelivery.hpp"
 #include "bp_policy.hpp"
 #include "bp_render.hpp"
+#include "bp_state.hpp"
 
 struct bp_handle {
     bp_config cfg;
@@ -79,6 +80,11 @@ struct bp_handle {
     bp_render_prim *r_prims = nullptr;// [BP_RENDER_MAX_PRIMS], layer 0 first
     int r_nunder = 0, r_nover = 0;
     bool r_table = false;
+    // state records (bp_state.hpp; bp_save_state / bp_load_state / bp_clone_state)
+    unsigned long long scen_hash = 0xCBF29CE484222325ull;   // FNV-1a over the scenario tables as uploaded by the loader
+    BpStateLayout st_layout;          // the segment table, built once at load time (state_setup)
+    BpStateSeg *st_table = nullptr;   // its device copy
+    unsigned long long st_layout_id = 0;
 };
 #define BP_COST_RING 1024
 
@@ -370,6 +376,15 @@ static int upload_trials(bp_handle *h, const std::vector<std::vector<bpgeom::Sha
             h_kind[o] = s.kind;
         }
     }
+    {   // scenario hash of the state records' layout id: the tables exactly as they are uploaded
+        unsigned long long sh = h->scen_hash;
+        sh = bp_fnv1a(h_nb.data(), sizeof(int) * h_nb.size(), sh); sh = bp_fnv1a(h_nv.data(), sizeof(int) * h_nv.size(), sh);
+        sh = bp_fnv1a(h_kind.data(), sizeof(int) * h_kind.size(), sh);
+        sh = bp_fnv1a(h_lv.data(), sizeof(d2) * h_lv.size(), sh); sh = bp_fnv1a(h_ln.data(), sizeof(d2) * h_ln.size(), sh);
+        sh = bp_fnv1a(h_mass.data(), sizeof(double4) * h_mass.size(), sh); sh = bp_fnv1a(h_pose.data(), sizeof(double4) * h_pose.size(), sh);
+        sh = bp_fnv1a(h_prop.data(), sizeof(double4) * h_prop.size(), sh);
+        h->scen_hash = sh;
+    }
     DevPtrs &D = h->D;
     int rc;
     int *d_nb, *d_nv, *d_kind; d2 *d_lv, *d_ln; double4 *d_mass, *d_pose, *d_prop;
@@ -634,6 +649,24 @@ static int upload_trials(bp_handle *h, const std::vector<std::vector<bpgeom::Sha
     return BP_OK;
 }
 
+// State records: the segment table over this handle's arrays, its device copy and the layout id (bp_state.hpp).  Called once, at the end of every loader.
+static int state_setup(bp_handle *h)
+{
+    const bool box = h->P.env_kind == BP_ENV_BOX;
+    const int cells = box ? h->B.SH * h->B.SW : 0;
+    h->st_layout = bp_state_layout(h->D, h->Q, h->nbcap, box, cells);
+    const BpStateLayout &L = h->st_layout;
+    if (L.nseg >= BP_STATE_MAXSEG || (L.bytes >> 4) >= 0xFFFFFFFFull) return fail(h, BP_EINVAL, "state record layout out of range");
+    unsigned long long id = bp_state_structure_id(L, h->P.env_kind, box ? h->bdcfg.task : 0, h->nbcap, cells);
+    if (box) id = bp_fnv1a(&h->bdcfg, sizeof(h->bdcfg), id);
+    else id = bp_fnv1a(&h->cfg, sizeof(h->cfg), id);
+    h->st_layout_id = bp_fnv1a_i64((long long)h->scen_hash, id);
+    int rc = dalloc(h, &h->st_table, (size_t)BP_STATE_MAXSEG);
+    if (rc) return rc;
+    HIPCHK(h, hipMemcpy(h->st_table, L.seg, sizeof(BpStateSeg) * L.nseg, hipMemcpyHostToDevice));
+    return BP_OK;
+}
+
 static int kind_of(int ctype, int group, int btype) { return ctype | (group << 8) | (btype << 16); }
 
 int bp_load_scenarios(bp_handle *h, int32_t T, int32_t F, int32_t V, const double *verts, const int32_t *counts,
@@ -666,7 +699,8 @@ int bp_load_scenarios(bp_handle *h, int32_t T, int32_t F, int32_t V, const doubl
             bodies.push_back(s);
         }
     }
-    return upload_trials(h, trials);
+    const int rc_up = upload_trials(h, trials);
+    return rc_up ? rc_up : state_setup(h);
 }
 
 int bp_load_maze(bp_handle *h, int32_t T, int32_t nbox, const double *centres, int32_t nwalls, const double *walls, const double *start)
@@ -731,7 +765,11 @@ int bp_load_maze(bp_handle *h, int32_t T, int32_t nbox, const double *centres, i
     if ((rc = dalloc(h, &d_raw, h->goal_raw.size()))) return rc;
     HIPCHK(h, hipMemcpy(d_raw, h->goal_raw.data(), sizeof(double) * h->goal_raw.size(), hipMemcpyHostToDevice));
     h->D.goal_raw = d_raw;
-    return upload_trials(h, trials);
+    h->scen_hash = bp_fnv1a(wall.data(), wall.size(), h->scen_hash);
+    h->scen_hash = bp_fnv1a(norm.data(), sizeof(double) * norm.size(), h->scen_hash);
+    h->scen_hash = bp_fnv1a(h->goal_raw.data(), sizeof(double) * h->goal_raw.size(), h->scen_hash);
+    const int rc_up = upload_trials(h, trials);
+    return rc_up ? rc_up : state_setup(h);
 }
 
 int bp_get_goal_map(bp_handle *h, double *out_host, int32_t *grid_h, int32_t *grid_w)
@@ -1482,6 +1520,7 @@ int bp_bd_load(bp_handle *h, int32_t T, int32_t nbox, const double *starts, cons
     if ((rc = dalloc(h, &d_rn, (size_t)nm * 4))) return rc;
     if ((rc = dalloc(h, &d_rchan, (size_t)B.local_px * B.local_px))) return rc;
     HIPCHK(h, hipMemcpy(d_mot, h->bd_map_of_trial.data(), sizeof(int) * T, hipMemcpyHostToDevice));
+    h->scen_hash = bp_fnv1a(h->bd_map_of_trial.data(), sizeof(int) * T, h->scen_hash);
     std::vector<int> first_trial_of_map(nm, -1);
     for (int t = 0; t < T; t++) if (first_trial_of_map[h->bd_map_of_trial[t]] < 0) first_trial_of_map[h->bd_map_of_trial[t]] = t;
     for (int m = 0; m < nm; m++) {
@@ -1491,6 +1530,11 @@ int bp_bd_load(bp_handle *h, int32_t T, int32_t nbox, const double *starts, cons
         HIPCHK(h, hipMemcpy(d_edt + (size_t)m * NW * 2, M.edt.data(), sizeof(unsigned short) * NW * 2, hipMemcpyHostToDevice));
         HIPCHK(h, hipMemcpy(d_rec + (size_t)m * NW, M.recept.data(), sizeof(float) * NW, hipMemcpyHostToDevice));
         HIPCHK(h, hipMemcpy(d_small + (size_t)m * NW, M.small_free.data(), NW, hipMemcpyHostToDevice));
+        h->scen_hash = bp_fnv1a(M.free_bits.data(), sizeof(unsigned) * words, h->scen_hash);
+        h->scen_hash = bp_fnv1a(M.thin_bits.data(), sizeof(unsigned) * words, h->scen_hash);
+        h->scen_hash = bp_fnv1a(M.edt.data(), sizeof(unsigned short) * NW * 2, h->scen_hash);
+        h->scen_hash = bp_fnv1a(M.recept.data(), sizeof(float) * NW, h->scen_hash);
+        h->scen_hash = bp_fnv1a(M.small_free.data(), NW, h->scen_hash);
         if (cf.task == 0) {
             const Shape &r = recepts[first_trial_of_map[m]];
             const std::vector<P2> wv = world_verts(r);
@@ -1498,6 +1542,7 @@ int bp_bd_load(bp_handle *h, int32_t T, int32_t nbox, const double *starts, cons
             for (int i = 0; i < 4; i++) { hp[i].x = wv[i].x; hp[i].y = wv[i].y; hn[i].x = r.normals[i].x; hn[i].y = r.normals[i].y; }
             HIPCHK(h, hipMemcpy(d_rp + (size_t)m * 4, hp, sizeof(hp), hipMemcpyHostToDevice));
             HIPCHK(h, hipMemcpy(d_rn + (size_t)m * 4, hn, sizeof(hn), hipMemcpyHostToDevice));
+            h->scen_hash = bp_fnv1a(hp, sizeof(hp), h->scen_hash);
         }
     }
     {   // robot_state_channel (box_delivery_env.py:124-131) * 255
@@ -1573,6 +1618,7 @@ int bp_bd_load(bp_handle *h, int32_t T, int32_t nbox, const double *starts, cons
     hipLaunchKernelGGL(k_bd_robot_map, dim3(T), dim3(BDR_THREADS), h->bd_rmap_lds, 0, h->P, h->D, h->B, h->Q, 1);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipDeviceSynchronize());
+    if ((rc = state_setup(h))) return rc;
     h->loaded = true;
     return BP_OK;
 }
@@ -1691,6 +1737,122 @@ int bp_render(bp_handle *h, const bp_render_args *args, const int32_t *env_ids, 
         HIPCHK(h, hipGetLastError());
     }
     return BP_OK;
+}
+
+// ---- state records (bp_state.hpp) --------------------------------------------------------------------------------------------------------------
+int64_t bp_state_bytes(const bp_handle *h)
+{
+    if (!h) return BP_EINVAL;
+    if (!h->loaded || !h->st_table) return BP_ESTATE;
+    return (int64_t)h->st_layout.bytes;
+}
+uint64_t bp_state_layout_id(const bp_handle *h) { return (h && h->loaded && h->st_table) ? h->st_layout_id : 0; }
+
+int bp_state_layout_query(int32_t env_kind, int32_t task, int32_t nbcap, int32_t map_cells, int32_t max_segments, int64_t *offsets_host,
+                          int64_t *bytes_host, int32_t *widths_host, int64_t *total_bytes, uint64_t *structure_id)
+{
+    if (env_kind < BP_ENV_SHIP_ICE || env_kind > BP_ENV_BOX || nbcap <= 0 || (nbcap & 7) || map_cells < 0 || max_segments < 0) return BP_EINVAL;
+    const bool box = env_kind == BP_ENV_BOX;
+    if ((box && map_cells == 0) || (!box && (map_cells != 0 || task != 0)) || task < 0 || task > 1) return BP_EINVAL;
+    DevPtrs D; BdPtrs Q;
+    memset(&D, 0, sizeof(D)); memset(&Q, 0, sizeof(Q));
+    const BpStateLayout L = bp_state_layout(D, Q, nbcap, box, map_cells);
+    for (int i = 0; i < L.nseg && i < max_segments; i++) {
+        if (offsets_host) offsets_host[i] = (int64_t)L.seg[i].off;
+        if (bytes_host) bytes_host[i] = (int64_t)L.seg[i].span;
+        if (widths_host) widths_host[i] = (int32_t)L.seg[i].width;
+    }
+    if (total_bytes) *total_bytes = (int64_t)L.bytes;
+    if (structure_id) *structure_id = bp_state_structure_id(L, env_kind, task, nbcap, map_cells);
+    return L.nseg;
+}
+
+// ids on the host (one synchronisation of the stream, as bp_render does for its ids): every id inside [0, E); no id of `dst` twice; no id of `dst` among `src`
+static int state_check_ids(bp_handle *h, const char *what, const int32_t *dst, const int32_t *src, int k, hipStream_t st, const uint8_t *records)
+{
+    std::vector<int> d(k), s(src ? k : 0);
+    std::vector<BpStateHeader> hdr(records ? k : 0);
+    HIPCHK(h, hipMemcpyAsync(d.data(), dst, sizeof(int) * k, hipMemcpyDeviceToHost, st));
+    if (src) HIPCHK(h, hipMemcpyAsync(s.data(), src, sizeof(int) * k, hipMemcpyDeviceToHost, st));
+    if (records) HIPCHK(h, hipMemcpy2DAsync(hdr.data(), sizeof(BpStateHeader), records, (size_t)h->st_layout.bytes, sizeof(BpStateHeader), (size_t)k, hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    std::vector<unsigned char> seen(h->num_envs, 0);
+    for (int i = 0; i < k; i++) {
+        if (d[i] < 0 || d[i] >= h->num_envs) return fail(h, BP_EINVAL, std::string(what) + ": env id " + std::to_string(d[i]) + " outside the batch");
+        if (src || records) {   // destinations: none twice
+            if (seen[d[i]]) return fail(h, BP_EINVAL, std::string(what) + ": destination env " + std::to_string(d[i]) + " is named twice");
+            seen[d[i]] = 1;
+        }
+    }
+    for (int i = 0; i < (src ? k : 0); i++) {
+        if (s[i] < 0 || s[i] >= h->num_envs) return fail(h, BP_EINVAL, std::string(what) + ": env id " + std::to_string(s[i]) + " outside the batch");
+        if (seen[s[i]]) return fail(h, BP_EINVAL, std::string(what) + ": env " + std::to_string(s[i]) + " is both a source and a destination");
+    }
+    for (int i = 0; i < (records ? k : 0); i++)
+        if (hdr[i].magic != BP_STATE_MAGIC || hdr[i].bytes != h->st_layout.bytes || hdr[i].layout_id != h->st_layout_id)
+            return fail(h, BP_EINVAL, std::string(what) + ": record " + std::to_string(i) + (hdr[i].magic != BP_STATE_MAGIC ? " is not a state record" :
+                        " was saved by a handle with another configuration, trials or capacities (layout id)"));
+    return BP_OK;
+}
+
+static int state_launch(const int MODE, bp_handle *h, const int *ids_a, const int *ids_b, unsigned char *records, int k, hipStream_t st)
+{
+    StateArgs A;
+    A.table = h->st_table; A.nseg = h->st_layout.nseg; A.nslots = (unsigned)(h->st_layout.bytes >> 4);
+    A.ids_a = ids_a; A.ids_b = ids_b; A.records = records;
+    A.hdr.magic = BP_STATE_MAGIC; A.hdr.bytes = h->st_layout.bytes; A.hdr.layout_id = h->st_layout_id; A.hdr.reserved = 0;
+    // four slots per thread in flight when that still leaves a workgroup for every wave slot or so of the device; one slot per thread for small k
+    const unsigned tiles4 = (A.nslots + 4 * BP_STATE_THREADS - 1) / (4 * BP_STATE_THREADS);
+    const bool wide = (unsigned long long)k * tiles4 >= 2048ull;
+    A.tiles = wide ? tiles4 : (A.nslots + BP_STATE_THREADS - 1) / BP_STATE_THREADS;
+    const int chunk = std::max(1, (int)((1u << 30) / A.tiles));   // records per launch
+    for (int r0 = 0; r0 < k; r0 += chunk) {
+        A.rec0 = r0;
+        const dim3 grid((unsigned)std::min(chunk, k - r0) * A.tiles), block(BP_STATE_THREADS);
+        if (MODE == STATE_PACK) { if (wide) hipLaunchKernelGGL(k_state_pack<4>, grid, block, 0, st, A); else hipLaunchKernelGGL(k_state_pack<1>, grid, block, 0, st, A); }
+        else if (MODE == STATE_UNPACK) { if (wide) hipLaunchKernelGGL(k_state_unpack<4>, grid, block, 0, st, A); else hipLaunchKernelGGL(k_state_unpack<1>, grid, block, 0, st, A); }
+        else { if (wide) hipLaunchKernelGGL(k_state_clone<4>, grid, block, 0, st, A); else hipLaunchKernelGGL(k_state_clone<1>, grid, block, 0, st, A); }
+        HIPCHK(h, hipGetLastError());
+    }
+    return BP_OK;
+}
+
+static int state_ready(bp_handle *h, const char *what)
+{
+    if (!h->loaded || !h->was_reset || !h->st_table) return fail(h, BP_ESTATE, std::string(what) + " before the first bp_reset");
+    return BP_OK;
+}
+
+int bp_save_state(bp_handle *h, const int32_t *env_ids, int32_t k, uint8_t *records, void *stream)
+{
+    if (!h) return BP_EINVAL;
+    if (int rc = state_ready(h, "bp_save_state")) return rc;
+    if (!env_ids || !records || k <= 0 || ((uintptr_t)records & 15u)) return fail(h, BP_EINVAL, "bp_save_state: null env_ids / records, k <= 0 or records not 16-byte aligned");
+    BP_DEVICE(h);
+    if (int rc = state_check_ids(h, "bp_save_state", env_ids, nullptr, k, (hipStream_t)stream, nullptr)) return rc;
+    return state_launch(STATE_PACK, h, env_ids, nullptr, records, k, (hipStream_t)stream);
+}
+
+int bp_load_state(bp_handle *h, const int32_t *env_ids, int32_t k, const uint8_t *records, int32_t flags, void *stream)
+{
+    if (!h) return BP_EINVAL;
+    if (int rc = state_ready(h, "bp_load_state")) return rc;
+    if (!env_ids || !records || k <= 0 || ((uintptr_t)records & 15u)) return fail(h, BP_EINVAL, "bp_load_state: null env_ids / records, k <= 0 or records not 16-byte aligned");
+    BP_DEVICE(h);
+    if (!(flags & BP_STATE_TRUSTED))
+        if (int rc = state_check_ids(h, "bp_load_state", env_ids, nullptr, k, (hipStream_t)stream, records)) return rc;
+    return state_launch(STATE_UNPACK, h, env_ids, nullptr, const_cast<uint8_t *>(records), k, (hipStream_t)stream);
+}
+
+int bp_clone_state(bp_handle *h, const int32_t *src_ids, const int32_t *dst_ids, int32_t k, int32_t flags, void *stream)
+{
+    if (!h) return BP_EINVAL;
+    if (int rc = state_ready(h, "bp_clone_state")) return rc;
+    if (!src_ids || !dst_ids || k <= 0) return fail(h, BP_EINVAL, "bp_clone_state: null ids or k <= 0");
+    BP_DEVICE(h);
+    if (!(flags & BP_STATE_TRUSTED))
+        if (int rc = state_check_ids(h, "bp_clone_state", dst_ids, src_ids, k, (hipStream_t)stream, nullptr)) return rc;
+    return state_launch(STATE_CLONE, h, src_ids, dst_ids, nullptr, k, (hipStream_t)stream);
 }
 
 int bp_get_num_bodies(bp_handle *h, int32_t *out_host)

@@ -60,6 +60,8 @@ struct DevParams {
 };
 
 // All device arrays of one handle.  "sc_" = scenario (per trial, read-only), others = per-env state.
+// State records (bp_state.hpp: bp_state_layout is the one table): every per-env member below is marked [record] = saved / restored / cloned with the env, or
+// [no record: why].  A new per-env array that a later API call's output can depend on is registered in bp_state_layout.
 struct DevPtrs {
     // scenarios [T][nbcap]...
     const int *sc_nb;        // [T] bodies in trial (ship + kept floes)
@@ -75,15 +77,16 @@ struct DevPtrs {
     const double *goal_raw;  // maze: un-normalised wavefront map (info['goal_dt']) [grid_h][grid_w]
     const double *maze_obs_map; // maze: dist_map with the wall raster in the sign bit (wall cells: -1.0), one load per cell for k_observe_maze
     // env state
-    int *e_trial, *e_episode, *e_nb, *e_err;
-    int *e_flags;            // [E] maze: bit0 wall_collision (sticky), bit1 prev_dist valid
-    double *e_prevdist;      // [E] maze: previous goal-map value
-    unsigned *e_stamp;
-    double *e_currdt, *e_total_work, *e_ke, *e_imp;
-    unsigned *e_cnt;         // [E][4] n_post_solve, n_contact_pts, n_first_contact, -
-    unsigned *e_cost;        // [E] wave cycles (>>8) the env's last step took: dispatch-order hint only
-    const int *order;        // [E] env handled by workgroup b (heaviest first), or null = identity
+    int *e_trial, *e_episode, *e_nb, *e_err;   // [record]; e_err: a load ORs the saved bits into the destination, as k_reset_copy does
+    int *e_flags;            // [E] maze: bit0 wall_collision (sticky), bit1 prev_dist valid  [record]
+    double *e_prevdist;      // [E] maze: previous goal-map value  [record]
+    unsigned *e_stamp;       // [record]
+    double *e_currdt, *e_total_work, *e_ke, *e_imp;   // [record]
+    unsigned *e_cnt;         // [E][4] n_post_solve, n_contact_pts, n_first_contact, -  [record]
+    unsigned *e_cost;        // [E] wave cycles (>>8) the env's last step took: dispatch-order hint only  [no record: results never depend on the order]
+    const int *order;        // [E] env handled by workgroup b (heaviest first), or null = identity  [no record: hint]
     // preemptive step scheduler (k_physics_step_sched): per XCD and level (= chunks of the step already done) a queue of waiting envs
+    // every sq_* array: [no record: step-local, rebuilt by k_sched_init, or a cumulative counter of the handle (sq_pairstat, sq_warn)]
     int *sq_items;           // [16][SQ_MAXLEV][sq_cap] env ids, -1 = not yet written (rows 0..7: XCD x, envs that run alone; 8..15: XCD x - 8, envs that were light when parked)
     int *sq_ctr;             // [16][SQ_MAXLEV + 2][2]: (head, tail) per level; row SQ_MAXLEV = (finished, total) of the XCD
     unsigned *sq_carry;      // [E][4] step-local state across chunks: yaw_violated, boundary_violated, work proxy, wave cycles >> 8
@@ -97,6 +100,7 @@ struct DevPtrs {
                              //     heavy (carried on alone in the same slot), heavy halves queued, light halves queued (split mates + yields), tasks declined at load, -
     int *sq_rescue;          // [1 + SQ_RESCUE] count and ids of the envs the scheduled launch left unfinished (k_sched_scan)
     int *sq_warn;            // [2] scheduler watchdog events, envs finished by the completion launch (cumulative; bp_sched_warnings)
+    // body state: all of it [record]
     d2 *pxy;                 // [E][nbcap] position of COG
     double *ang;             // [E][nbcap]
     d2 *rot;                 // [E][nbcap] cos, sin
@@ -106,10 +110,10 @@ struct DevPtrs {
     unsigned short *adj;     // [E][nbcap][KADJ]
     unsigned char *adjn;     // [E][nbcap]
     unsigned long long *hint; // [E][nbcap][KADJ] cached plane-search winners of the pair behind each neighbour slot (HW_* below)
-    // persisted arbiter slots [E][ACAP]
+    // persisted arbiter slots [E][ACAP]: all [record]
     unsigned *a_key, *a_stamp, *a_sc, *a_h0, *a_h1;
     double *a_d;             // [E][ACAP][14] jn0 jt0 jn1 jt1 nx ny r1x0 r1y0 r2x0 r2y0 r1x1 r1y1 r2x1 r2y1
-    // result of the last step per env (read by k_episode_metrics) and the on-device episode metrics
+    // result of the last step per env (read by k_episode_metrics) and the on-device episode metrics: all [record]
     double *e_lastrew;       // [E]
     int *e_lastflag;         // [E] bit0 terminated, bit1 trial_success
     double *m_acc;           // [E][8] episode reward, path length l0, previous rounded x, y, L, steps, total_work, success
@@ -118,8 +122,8 @@ struct DevPtrs {
     double *m_sum;           // [E][BP_EPM_COUNT] row fields summed over all finished episodes
     unsigned *m_count;       // [E] finished episodes
     unsigned char *m_open;   // [E] an episode is running (reset seen, not yet terminated)
-    unsigned long long *clk; // [8][2] per XCD: shader-clock counter (s_memtime) and 100 MHz reference (s_memrealtime) stamped after a physics launch by a thread of that XCD
-    // debug
+    unsigned long long *clk; // [8][2] per XCD: shader-clock counter (s_memtime) and 100 MHz reference (s_memrealtime) stamped after a physics launch by a thread of that XCD  [no record: per device, not per env]
+    // debug  [no record: diagnostics of the handle]
     double *dbg;             // optional [substeps][nbcap][3] pose trace of env dbg_env
     int dbg_env;
     unsigned long long *prof; // optional [E][24] phase cycle counters (BP_PROF builds)

@@ -171,6 +171,18 @@ class AreaClearingEnv(Env):
         return (self._result(info), float(self._b.reward[0].item()), bool(self._b.terminated[0].item()),
                 bool(self._b.truncated[0].item()), info)
 
+    _STATE_FIELDS = ("t", "episode_idx", "box_clearance_statuses")
+
+    def save_state(self):
+        """The whole env between two steps as an ``EnvState`` (benchpush_amd/state.py): the device state record plus this adapter's own fields."""
+        from ..state import adapter_save
+        return adapter_save(self, self._STATE_FIELDS)
+
+    def restore_state(self, state):
+        """Back to a state of save_state(): the following steps repeat bit for bit what followed the save."""
+        from ..state import adapter_restore
+        adapter_restore(self, state, self._STATE_FIELDS)
+
     def render(self, mode="human", close=False):
         """rgb_array: the frame of this env with the controller's current waypoints as the path (numpy [H, W, 3]; benchpush_amd/render.py).
         human: no window; with render.show set, every anim.plot_steps-th step writes <output_dir>/t<episode_idx>/<t>.png (area_clearing.py:1145-1149),

@@ -199,6 +199,18 @@ class BoxDeliveryEnv(Env):
         return (self._b.obs[0].cpu().numpy(), float(self._b.reward[0].item()), bool(self._b.terminated[0].item()),
                 bool(self._b.truncated[0].item()), info)
 
+    _STATE_FIELDS = ("t", "episode_idx", "box_clearance_statuses")
+
+    def save_state(self):
+        """The whole env between two steps as an ``EnvState`` (benchpush_amd/state.py): the device state record plus this adapter's own fields."""
+        from ..state import adapter_save
+        return adapter_save(self, self._STATE_FIELDS)
+
+    def restore_state(self, state):
+        """Back to a state of save_state(): the following steps repeat bit for bit what followed the save."""
+        from ..state import adapter_restore
+        adapter_restore(self, state, self._STATE_FIELDS)
+
     def render(self, mode="human", close=False):
         """rgb_array: the frame of this env with the controller's current waypoints as the path (numpy [H, W, 3]; benchpush_amd/render.py).
         human: no window and no snapshot (the reference's save branch is disabled, box_delivery_env.py:1275): warns once, returns None."""

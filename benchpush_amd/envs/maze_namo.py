@@ -193,6 +193,18 @@ class MazeNAMO(Env):
         return dump_channels(self.cfg.output_dir, self.episode_idx, self.t,
                              {"footprint": o[0], "movable_obs": o[1], "fixed_obs": o[2], "distance_map": gn, "local_distance_map": o[3]})
 
+    _STATE_FIELDS = ("t", "total_work", "episode_idx", "path", "obstacles", "wall_collision")
+
+    def save_state(self):
+        """The whole env between two steps as an ``EnvState`` (benchpush_amd/state.py): the device state record plus this adapter's own fields."""
+        from ..state import adapter_save
+        return adapter_save(self, self._STATE_FIELDS)
+
+    def restore_state(self, state):
+        """Back to a state of save_state(): the following steps repeat bit for bit what followed the save."""
+        from ..state import adapter_restore
+        adapter_restore(self, state, self._STATE_FIELDS)
+
     def update_path(self, new_path, scatter=False):
         self.path = new_path
 

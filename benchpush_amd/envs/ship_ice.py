@@ -68,6 +68,70 @@ class _BatchedBase:
         self.info = torch.zeros((E, _lib.INFO_COUNT), dtype=torch.float64, device=dv)
         self._actions = torch.zeros(E, dtype=torch.float64, device=dv)
 
+    # -- saving, restoring and forking (include/benchpush_amd.h: state records) ---------------------------
+    _OUT_ROWS = ("obs", "reward", "terminated", "truncated", "info")
+
+    def _env_ids(self, env_ids):
+        if env_ids is None:
+            return torch.arange(self.num_envs, dtype=torch.int32, device=self.device)
+        return torch.as_tensor(env_ids).reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
+
+    def state_bytes(self):
+        """Bytes of one state record of this handle."""
+        n = int(self.L.bp_state_bytes(self.h))
+        _lib.check(self.L, self.h, min(n, 0), "bp_state_bytes")
+        return n
+
+    def state_layout_id(self):
+        """The handle's layout id: records are exchanged between handles with equal ids (same configuration, same trials; any number of envs)."""
+        return int(self.L.bp_state_layout_id(self.h))
+
+    def save_state(self, env_ids=None):
+        """The complete state of the envs `env_ids` (None: all) between two steps as an ``EnvState`` on the device: one record per env, written by one
+        kernel launch, plus the envs' rows of obs / reward / terminated / truncated / info.  Raises BpError before the first reset or for an id outside
+        the batch.  Synchronises the stream once (the ids are checked on the host)."""
+        from ..state import EnvState
+        ids = self._env_ids(env_ids)
+        k = int(ids.numel())
+        rec = torch.empty((k, self.state_bytes()), dtype=torch.uint8, device=self.device)
+        _lib.check(self.L, self.h, self.L.bp_save_state(self.h, _ptr(ids), k, _ptr(rec), self._stream()), "bp_save_state")
+        idx = ids.long()   # (indexed only after the library has accepted the ids)
+        return EnvState(rec, *[getattr(self, n)[idx] for n in self._OUT_ROWS], self.state_layout_id(), ids.clone())
+
+    def restore_state(self, state, env_ids=None, trusted=False):
+        """Put the saved envs of `state` into the envs `env_ids` (None: the envs they were saved from) -- of this handle or of any handle created with the
+        same configuration and trials.  The envs continue bit for bit as the saved ones would have; their rows of obs / reward / terminated / truncated /
+        info are put back as well.  Raises BpError, with no env touched, for an id outside the batch, a repeated id or records of another layout.
+        trusted=True skips those checks and the host synchronisation they need."""
+        ids = self._env_ids(state.env_ids if env_ids is None else env_ids)
+        k = int(ids.numel())
+        if k != len(state):
+            raise ValueError("restore_state: %d env ids for %d saved envs" % (k, len(state)))
+        if state.device != self.device:
+            state = state.to(self.device)
+        rec = state.records.contiguous()
+        if rec.dtype != torch.uint8 or rec.dim() != 2 or rec.shape[1] != self.state_bytes():
+            raise _lib.BpError("restore_state failed: BP_EINVAL (-1) records of %s bytes, this handle's are %d" % (tuple(rec.shape[1:]), self.state_bytes()))
+        _lib.check(self.L, self.h, self.L.bp_load_state(self.h, _ptr(ids), k, _ptr(rec), _lib.STATE_TRUSTED if trusted else 0, self._stream()),
+                   "bp_load_state")
+        idx = ids.long()
+        for n in self._OUT_ROWS:
+            getattr(self, n)[idx] = getattr(state, n)
+
+    def clone_envs(self, src_ids, dst_ids, trusted=False):
+        """Fork: env dst_ids[i] becomes a bit-exact copy of env src_ids[i] (one kernel launch, no staging buffer); a source may be repeated (fan-out).
+        The output rows follow.  Raises BpError, with no env touched, for an id outside the batch, a repeated destination or a destination that is also a
+        source; trusted=True skips those checks and the host synchronisation they need."""
+        src, dst = self._env_ids(src_ids), self._env_ids(dst_ids)
+        if src.numel() != dst.numel():
+            raise ValueError("clone_envs: %d sources for %d destinations" % (src.numel(), dst.numel()))
+        _lib.check(self.L, self.h, self.L.bp_clone_state(self.h, _ptr(src), _ptr(dst), int(src.numel()), _lib.STATE_TRUSTED if trusted else 0,
+                                                         self._stream()), "bp_clone_state")
+        s, d = src.long(), dst.long()
+        for n in self._OUT_ROWS:
+            t = getattr(self, n)
+            t[d] = t[s]
+
 
 class BatchedShipIceEnv(_BatchedBase):
     """E independent ship-ice environments on one GPU.
@@ -489,6 +553,18 @@ class ShipIceEnv(Env):
             o = self._b.observe_global()[0].cpu().numpy()   # [occupancy, footprint] (ship_ice_env.py:405)
             ch = {"con": o[0], "footprint": o[1]}
         return dump_channels(self.cfg.output_dir, self.episode_idx, self.t, ch)
+
+    _STATE_FIELDS = ("t", "total_work", "episode_idx", "path", "obstacles")
+
+    def save_state(self):
+        """The whole env between two steps as an ``EnvState`` (benchpush_amd/state.py): the device state record plus this adapter's own fields."""
+        from ..state import adapter_save
+        return adapter_save(self, self._STATE_FIELDS)
+
+    def restore_state(self, state):
+        """Back to a state of save_state(): the following steps repeat bit for bit what followed the save."""
+        from ..state import adapter_restore
+        adapter_restore(self, state, self._STATE_FIELDS)
 
     def update_path(self, new_path):
         self.path = new_path

@@ -188,6 +188,24 @@ class BatchedVecEnv(_Base):
         return (self._obs_out(obuf), hb["rew"].numpy().copy(), done_h,
                 LazyInfos(self.info_keys, hb["info"].numpy().copy(), done_h, hb["trunc"].numpy().copy(), self._term_obs, True))
 
+    # -- saving and restoring (benchpush_amd/state.py) ----------------------------------------------------
+    def save_state(self, env_ids=None):
+        """``env.save_state(env_ids)`` plus this wrapper's own per-env rows: the TimeLimit counters and the current terminal-observation rows."""
+        s = self.env.save_state(env_ids)
+        idx = s.env_ids.long()
+        s.extra["vec_steps"] = self._steps[idx]
+        s.extra["vec_term_obs"] = self._term_obs[idx]
+        return s
+
+    def restore_state(self, state, env_ids=None, trusted=False):
+        """``env.restore_state(state, env_ids)``; the TimeLimit counters and terminal-observation rows of those envs are put back as well."""
+        self.env.restore_state(state, env_ids, trusted=trusted)
+        idx = self.env._env_ids(state.env_ids if env_ids is None else env_ids).long()
+        dv = self.env.device
+        if "vec_steps" in state.extra:
+            self._steps[idx] = state.extra["vec_steps"].to(dv)
+            self._term_obs[idx] = state.extra["vec_term_obs"].to(dv)
+
     def step(self, actions):
         self.step_async(actions)
         return self.step_wait()

@@ -401,6 +401,36 @@ int bp_set_render_table(bp_handle *h, int32_t T, int32_t nslot, const int32_t *o
 int bp_render(bp_handle *h, const bp_render_args *args, const int32_t *env_ids, int32_t k, const double *paths, const int32_t *path_len,
               uint8_t *out, void *stream);
 
+/* ---- saving, restoring and forking environments (state records) ----
+ * Between two steps an env is a fixed-size byte image, the state record: a 32-byte header (magic, record size, 64-bit layout id, 8 reserved bytes) and one
+ * segment per persistent per-env array (body state, the 64 arbiter slots, the per-env scalars, the last step's reward / flags, the episode metrics;
+ * box-delivery / area-clearing: box bookkeeping, waypoints and the robot's distance map), every segment on a 16-byte boundary.  Left out: dispatch-order
+ * hints, scheduler queues, timers and cumulative counters of the handle -- results never depend on them.  The layout id hashes the env kind and task, the
+ * capacities (body slots, BP_MAXV, neighbour and arbiter slots, box and waypoint slots, map cells), the bytes of the handle's configuration struct (padding
+ * included: zero it) and the scenario tables as uploaded by the loader; the number of envs and env_id_offset are NOT part of it, so a record may be loaded
+ * into any handle created with the same configuration and the same trials.  Records do not survive another configuration, other trials or another library build.
+ *   env_ids / src_ids / dst_ids  device int32 [k], ids in [0, E) (the reset templates are not addressable)
+ *   records                      device uint8 [k][record bytes], 16-byte aligned
+ * All work is enqueued on `stream` after the work already queued there.  BP_ESTATE before the first reset.  With flags == 0 the calls synchronise `stream`
+ * once to check their arguments on the host and return BP_EINVAL WITHOUT touching any env for: an id outside [0, E), a destination named twice, (clone) a
+ * destination that is also a source, (load) a header with a wrong magic, size or layout id.  Saving always checks its ids.  BP_STATE_TRUSTED skips checks and
+ * synchronisation (planners that call this in a loop); what an unchecked bad argument does is undefined.  A source may be repeated (fan-out 1 -> n).
+ * A restored env continues exactly (bit for bit) as the saved one would have until its episode ends; per-env error bits saved in a record are OR-ed into the
+ * destination's, never cleared.  At its next reset the DESTINATION env draws its trial and its random_start pose from its OWN global id and the restored
+ * episode counter: trial (env_id_offset + env + episode) % T, like every other reset of that env. */
+#define BP_STATE_TRUSTED 1
+int64_t bp_state_bytes(const bp_handle *h);          /* bytes of one record; < 0 before the scenarios are loaded */
+uint64_t bp_state_layout_id(const bp_handle *h);     /* 0 before the scenarios are loaded */
+int bp_save_state(bp_handle *h, const int32_t *env_ids, int32_t k, uint8_t *records, void *stream);
+int bp_load_state(bp_handle *h, const int32_t *env_ids, int32_t k, const uint8_t *records, int32_t flags, void *stream);
+int bp_clone_state(bp_handle *h, const int32_t *src_ids, const int32_t *dst_ids, int32_t k, int32_t flags, void *stream);
+/* The record layout as a pure function (no GPU, no handle): env_kind BP_ENV_*, task (box handles: 0 box-delivery, 1 area-clearing), nbcap body slots
+ * (a multiple of 8), map_cells = cells of a box handle's small-map window (0 otherwise).  Returns the number of segments (the header is segment 0) or a negative
+ * BP_E*; writes the first max_segments rows of offsets_host / bytes_host (int64: offset in the record, bytes per env) and widths_host (int32: widest access
+ * in bytes), the record size and the part of the layout id that these shapes decide.  Any pointer may be NULL. */
+int bp_state_layout_query(int32_t env_kind, int32_t task, int32_t nbcap, int32_t map_cells, int32_t max_segments, int64_t *offsets_host,
+                          int64_t *bytes_host, int32_t *widths_host, int64_t *total_bytes, uint64_t *structure_id);
+
 const char *bp_last_error(const bp_handle *h);
 int32_t bp_abi_version(void);
 int32_t bp_sizeof_config(void);   /* sizeof(bp_config), so a binding can verify its struct layout */
