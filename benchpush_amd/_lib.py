@@ -28,13 +28,21 @@ EXPORTS = ["bp_abi_version", "bp_create", "bp_destroy", "bp_load_scenarios", "bp
            "bp_copy_rows_masked", "bp_pair_mode", "bp_get_pair_stats", "bp_bd_get_stragglers",
            "bp_device_shared", "bp_launch_policy_query", "bp_bd_budget", "bp_get_cost_stats", "bp_bd_get_cycle_skips",
            "bp_sizeof_render_args", "bp_sizeof_render_prim", "bp_set_render_table", "bp_render",
-           "bp_state_bytes", "bp_state_layout_id", "bp_save_state", "bp_load_state", "bp_clone_state", "bp_state_layout_query"]
+           "bp_state_bytes", "bp_state_layout_id", "bp_save_state", "bp_load_state", "bp_clone_state", "bp_state_layout_query",
+           "bp_sizeof_swath_config", "bp_swath_cost"]
+SWATH_CLIP, SWATH_REJECT = 0, 1
+SWATH_MAX_WORDS = 4096   # bp_swath_cost: H * ceil(W / 64) at most (the swath's bit image lives in LDS)
 STATE_TRUSTED = 1    # BP_STATE_TRUSTED: bp_load_state / bp_clone_state skip the argument checks and the synchronisation
 
 
 class BpCostmapConfig(C.Structure):
     _fields_ = [("scale", C.c_double), ("m", C.c_int32), ("n", C.c_int32), ("alpha", C.c_double), ("ship_mass", C.c_double),
                 ("horizon", C.c_double), ("margin", C.c_int32), ("pad_", C.c_int32)]
+
+
+class BpSwathConfig(C.Structure):
+    _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("K", C.c_int32), ("P", C.c_int32), ("nv", C.c_int32), ("outside", C.c_int32),
+                ("map_stride", C.c_int64)]
 
 
 class BpConfig(C.Structure):
@@ -184,6 +192,11 @@ def load():
         L.bp_load_state.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, vp]
         L.bp_clone_state.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, vp]
         L.bp_state_layout_query.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_uint64)]
+    if hasattr(L, "bp_swath_cost"):   # swath costs (absent from older builds loaded for same-box comparisons)
+        L.bp_sizeof_swath_config.restype = C.c_int32
+        if L.bp_sizeof_swath_config() != C.sizeof(BpSwathConfig):
+            raise BpError("bp_swath_config layout mismatch between _lib.BpSwathConfig and the library")
+        L.bp_swath_cost.argtypes = [vp, C.POINTER(BpSwathConfig), vp, vp, vp, vp, vp, vp, vp, vp]
     _lib = L
     return L
 

@@ -39,3 +39,17 @@ class CostMap:
         spy = np.broadcast_to(np.asarray(ship_pos_y, np.float64), (E,)).copy()
         self.cost_maps = self._b.cost_maps(self.scale, self.m, self.n, self.alpha, self.ship_mass, self._horizon_m, self.margin, spy, vs)
         self.cost_map = self.cost_maps[0].cpu().numpy()
+
+    def swath_cost(self, path, ship_vertices):
+        """``compute_swath_cost(cost_map, path, ship_vertices)`` of the reference (common/swath.py:114-163) for environment 0 over the map of the last
+        ``update()``, computed on the device (``BatchedShipIceEnv.swath_costs``): path [n, 3] = (x, y, theta) in cells, ship_vertices [nv, 2] in cells
+        (``Ship.vertices``).  Returns (swath: bool [H, W], cost: float)."""
+        import torch
+        if self.cost_maps is None:
+            raise ValueError("CostMap.swath_cost needs a cost map: call update() first")
+        b = self._b
+        p = np.ascontiguousarray(np.asarray(path, np.float64).reshape(-1, 3))
+        paths = torch.from_numpy(p).to(b.device)[None, None].expand(b.num_envs, 1, len(p), 3).contiguous()
+        fp = torch.from_numpy(np.ascontiguousarray(np.asarray(ship_vertices, np.float64).reshape(-1, 2))).to(b.device)
+        costs, swaths = b.swath_costs(paths, fp, self.cost_maps, return_swaths=True)
+        return swaths[0, 0].cpu().numpy().astype(bool), float(costs[0, 0].item())

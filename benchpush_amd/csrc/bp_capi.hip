@@ -21,6 +21,7 @@
 #include "bp_policy.hpp"
 #include "bp_render.hpp"
 #include "bp_state.hpp"
+#include "bp_swath.hpp"
 
 struct bp_handle {
     bp_config cfg;
@@ -1330,6 +1331,31 @@ int bp_costmap_update(bp_handle *h, const bp_costmap_config *cfg, const double *
     if (groups > 0)
         hipLaunchKernelGGL(k_costmap, dim3(h->num_envs, groups), dim3(256), 0, st, h->P, h->D, cfg->scale, H, W, cfg->alpha, cfg->ship_mass,
                            cfg->horizon > 0 ? cfg->horizon * cfg->scale : 0.0, ship_pos_y, vs, out);
+    HIPCHK(h, hipGetLastError());
+    return BP_OK;
+}
+int32_t bp_sizeof_swath_config(void) { return (int32_t)sizeof(bp_swath_config); }
+int bp_swath_cost(bp_handle *h, const bp_swath_config *cfg, const double *cost_maps, const double *paths, const int32_t *lengths, const int32_t *rows,
+                  const double *footprint, double *costs, uint8_t *swaths, void *stream)
+{
+    if (!h || !cfg || !cost_maps || !paths || !footprint || !costs) return BP_EINVAL;
+    if (!h->loaded || !h->was_reset) return fail(h, BP_ESTATE, "bp_swath_cost before bp_load_scenarios/bp_reset");
+    if (h->P.env_kind != BP_ENV_SHIP_ICE) return fail(h, BP_EINVAL, "bp_swath_cost: ship-ice handles only");
+    if (cfg->H <= 0 || cfg->W <= 0 || cfg->K <= 0 || cfg->P <= 0) return fail(h, BP_EINVAL, "bp_swath_cost: H, W, K and P must be positive");
+    if (cfg->nv < 3 || cfg->nv > BP_MAXV) return fail(h, BP_EINVAL, "bp_swath_cost: footprint of 3 .. 20 vertices");
+    if (cfg->outside != BP_SWATH_CLIP && cfg->outside != BP_SWATH_REJECT) return fail(h, BP_EINVAL, "bp_swath_cost: unknown outside mode");
+    const long long WW = ((long long)cfg->W + 63) / 64, words = (long long)cfg->H * WW;
+    if (words > BP_SWATH_MAX_WORDS) return fail(h, BP_EINVAL, "bp_swath_cost: grid above the LDS limit (H * ceil(W / 64) <= 4096)");
+    const long long cells = (long long)cfg->H * cfg->W, ncand = (long long)h->num_envs * cfg->K;
+    if (cfg->map_stride < 0 || (cfg->map_stride > 0 && cfg->map_stride < cells)) return fail(h, BP_EINVAL, "bp_swath_cost: bad map_stride");
+    if (ncand > 0x7FFFFFFFll || (long long)cfg->P * 3 > 0x7FFFFFFFll) return fail(h, BP_EINVAL, "bp_swath_cost: too many candidates or samples");
+    BP_DEVICE(h);
+    SwathArgs A;
+    A.H = cfg->H; A.W = cfg->W; A.K = cfg->K; A.P = cfg->P; A.nv = cfg->nv; A.WW = (int)WW; A.outside = cfg->outside;
+    A.vec4 = swaths && (((uintptr_t)swaths) & 3u) == 0 && (cells & 3) == 0;
+    A.map_stride = cfg->map_stride;
+    A.maps = cost_maps; A.paths = paths; A.fp = footprint; A.lengths = lengths; A.rows = rows; A.costs = costs; A.swaths = swaths;
+    hipLaunchKernelGGL(k_swath_cost, dim3((unsigned)ncand), dim3(64), (size_t)words * 8, (hipStream_t)stream, A);
     HIPCHK(h, hipGetLastError());
     return BP_OK;
 }

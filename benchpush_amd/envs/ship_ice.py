@@ -316,6 +316,63 @@ class BatchedShipIceEnv(_BatchedBase):
                                                             _ptr(out), self._stream()), "bp_costmap_update")
         return out
 
+    def swath_costs(self, paths, footprint, cost_maps, lengths=None, rows=None, outside="clip", return_swaths=False, out=None):
+        """Cost of K candidate paths per env over the cost maps, on the device (bp_swath_cost): the sum of `cost_maps` over the cells that the ship
+        footprint sweeps along each path -- the reference's ``compute_swath_cost`` (common/swath.py:114-163), the sum inside ``AStar.get_swath_cost``
+        and the two sums of ``Path.update`` -- with no copy to the host.  All arguments are contiguous device tensors:
+
+        paths      float64 [E, K, P, 3]: samples (x, y, theta) in cost-map cells / radians
+        footprint  float64 [nv, 2] in cells, 3 <= nv <= 20, any simple polygon (``planning.ship_footprint``)
+        cost_maps  float64 [E, H, W] (``cost_maps()``), or one [H, W] map shared by all envs; H * ceil(W / 64) <= 4096
+        lengths    int32 [E, K] or None: the samples of each candidate that count (clamped to [0, P])
+        rows       int32 [E, 2] or [E, K, 2] or None: the swath is restricted to rows lo <= r < hi (each clamped to [0, H])
+        outside    "clip": cells off the map are ignored, like compute_swath_cost.  "reject": +inf for a candidate with any footprint vertex of a counted
+                   sample outside [0, W-1] x [0, H-1] -- what A*'s ``return np.inf`` is for, stated on the vertices so that it is exact; it is stricter than
+                   the reference's pixel rule by less than one cell.
+        out        None, a float64 [E, K] tensor for the costs, or (costs, swaths) with swaths uint8 [E, K, H, W]
+
+        Returns costs [E, K], or (costs, swaths) with return_swaths (0 / 1 masks, row window applied).  A candidate with a non-finite counted sample costs
+        NaN and has an empty mask; a finite sample beyond 1e15 lies off the map.  The sum runs over a row's columns, then over the rows, in ascending
+        order: equal inputs give equal bits.  Raises ValueError, before any launch, for a wrong dtype, device, shape or a non-contiguous tensor; BpError
+        for what the library refuses (footprint size, grid above the LDS limit, not a ship-ice env).  Touches no environment state."""
+        E = self.num_envs
+
+        def need(t, name, dtype, shapes):
+            if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != self.device or not t.is_contiguous():
+                raise ValueError("swath_costs: %s must be a contiguous %s tensor on %s" % (name, dtype, self.device))
+            if not any(len(sh) == t.dim() and all(a is None or a == b for a, b in zip(sh, t.shape)) for sh in shapes):
+                raise ValueError("swath_costs: %s has shape %s, expected %s" % (name, tuple(t.shape), " or ".join(str(list(sh)) for sh in shapes)))
+
+        if outside not in ("clip", "reject"):
+            raise ValueError("swath_costs: outside must be 'clip' or 'reject'")
+        need(paths, "paths", torch.float64, [(E, None, None, 3)])
+        K, P = int(paths.shape[1]), int(paths.shape[2])
+        need(footprint, "footprint", torch.float64, [(None, 2)])
+        need(cost_maps, "cost_maps", torch.float64, [(E, None, None), (None, None)])
+        H, W = int(cost_maps.shape[-2]), int(cost_maps.shape[-1])
+        if lengths is not None:
+            need(lengths, "lengths", torch.int32, [(E, K)])
+        if rows is not None:
+            need(rows, "rows", torch.int32, [(E, 2), (E, K, 2)])
+            if rows.dim() == 2:
+                rows = rows[:, None, :].expand(E, K, 2).contiguous()
+        costs, swaths = out if isinstance(out, (tuple, list)) else (out, None)
+        if costs is not None:
+            need(costs, "out", torch.float64, [(E, K)])
+        if swaths is not None:
+            need(swaths, "out[1]", torch.uint8, [(E, K, H, W)])
+        if min(K, P, H, W) <= 0:
+            raise ValueError("swath_costs: empty paths or cost maps")
+        if costs is None:
+            costs = torch.empty((E, K), dtype=torch.float64, device=self.device)
+        if return_swaths and swaths is None:
+            swaths = torch.empty((E, K, H, W), dtype=torch.uint8, device=self.device)
+        cfg = _lib.BpSwathConfig(H=H, W=W, K=K, P=P, nv=int(footprint.shape[0]), outside=_lib.SWATH_REJECT if outside == "reject" else _lib.SWATH_CLIP,
+                                 map_stride=H * W if cost_maps.dim() == 3 else 0)
+        _lib.check(self.L, self.h, self.L.bp_swath_cost(self.h, C.byref(cfg), _ptr(cost_maps), _ptr(paths), _ptr(lengths), _ptr(rows), _ptr(footprint),
+                                                        _ptr(costs), _ptr(swaths) if return_swaths else None, self._stream()), "bp_swath_cost")
+        return (costs, swaths) if return_swaths else costs
+
     def episode_metrics(self):
         """On-device ShipIceMetric: (rows [E, 6] float64 = efficiency, effort, episode reward, success, episode length, total_work of
         each env's most recently finished episode; counts [E] int32 = episodes finished so far).  Device tensors; rows of envs with

@@ -431,6 +431,38 @@ int bp_clone_state(bp_handle *h, const int32_t *src_ids, const int32_t *dst_ids,
 int bp_state_layout_query(int32_t env_kind, int32_t task, int32_t nbcap, int32_t map_cells, int32_t max_segments, int64_t *offsets_host,
                           int64_t *bytes_host, int32_t *widths_host, int64_t *total_bytes, uint64_t *structure_id);
 
+/* ---- swath costs of candidate paths over the cost maps ----
+ * compute_swath_cost of the reference (common/swath.py:114-163; the sum inside AStar.get_swath_cost and Path.update) for K candidate paths of every env in
+ * one launch (DESIGN.md "Swath costs" states the semantics exactly).  All arrays are device memory:
+ *   cost_maps  double [E][H][W] with map_stride doubles between the envs' maps, or one [H][W] map for all envs with map_stride 0
+ *   paths      double [E][K][P][3]: samples (x, y, theta) in cost-map cells / radians
+ *   lengths    int32 [E][K] or NULL (all P): samples that count, clamped to [0, P] on the device
+ *   rows       int32 [E][K][2] or NULL (all rows): the swath is restricted to rows lo <= r < hi, each bound clamped to [0, H] on the device
+ *   footprint  double [nv][2] in cells, 3 <= nv <= BP_MAXV (20), any simple polygon
+ *   costs      double [E][K]
+ *   swaths     uint8 [E][K][H][W] (0 / 1, row window applied) or NULL
+ * A pixel (row r, column q) is covered by a sample iff skimage's point_in_polygon holds for (x = q, y = r) and the vertices
+ * (x + (c*vx - s*vy), y + (s*vx + c*vy)), (s, c) the library's deterministic sin / cos of theta; a candidate's swath is the union over its counted
+ * samples.  The cost adds the map's covered cells per row in ascending column order and the row sums in ascending row order, each from +0.0.
+ * BP_SWATH_CLIP ignores what lies off the map; BP_SWATH_REJECT gives +inf if any transformed vertex of a counted sample lies outside
+ * [0, W-1] x [0, H-1] (the mask is still the clipped one).  A non-finite component in a counted sample: NaN, empty mask.  A finite sample with |x|, |y|
+ * or |theta| above 1e15 counts as off the map as a whole.
+ * The bit image of the swath lives in LDS: H * ceil(W / 64) <= 4096 is required (380 x 60: 380).  BP_EINVAL, with nothing launched or written, for a
+ * NULL required pointer, H, W, K, P <= 0, nv outside [3, 20], a grid above that limit, an unknown mode, 0 < map_stride < H * W or a handle that is
+ * not ship-ice; BP_ESTATE before load and reset.  Reads the handle's device only: no environment state is touched.  Enqueued on `stream`. */
+#define BP_SWATH_CLIP 0
+#define BP_SWATH_REJECT 1
+typedef struct bp_swath_config {
+    int32_t H, W;           /* rows and columns of a cost map */
+    int32_t K, P;           /* candidates per env, samples per candidate */
+    int32_t nv;             /* footprint vertices */
+    int32_t outside;        /* BP_SWATH_CLIP / BP_SWATH_REJECT */
+    int64_t map_stride;     /* doubles between the envs' maps; 0: one map shared by all */
+} bp_swath_config;
+int32_t bp_sizeof_swath_config(void);
+int bp_swath_cost(bp_handle *h, const bp_swath_config *cfg, const double *cost_maps, const double *paths, const int32_t *lengths, const int32_t *rows,
+                  const double *footprint, double *costs, uint8_t *swaths, void *stream);
+
 const char *bp_last_error(const bp_handle *h);
 int32_t bp_abi_version(void);
 int32_t bp_sizeof_config(void);   /* sizeof(bp_config), so a binding can verify its struct layout */
