@@ -44,15 +44,7 @@
 #define BP_DBGP(bit) false
 #define BP_TRACE_ON(D) false
 #endif
-struct ArbReg {
-    unsigned key, stamp, h0, h1;
-    int state, count, level, rank;
-    double jn0, jt0, jn1, jt1;
-    d2 n, r1_0, r2_0, r1_1, r2_1;
-    double ma, ia, mb, ib;
-    double e, u;               // elasticity / friction products of the two shapes (cpArbiterUpdate)
-    int slotA, slotB;          // velocity slots of the two bodies
-};
+#include "bp_contact.hpp"   // ArbReg, Manifold, apply_contact_impulses and the lane-local contact arithmetic shared with substep_pair()
 
 struct EnvCtx {
     int nb;
@@ -153,8 +145,6 @@ __device__ __forceinline__ int slot_get(const LdsCtx &L, SubState &S, const d2 *
     return s;
 }
 
-struct Manifold { int count; d2 n; d2 p1_0, p2_0, p1_1, p2_1; unsigned h0, h1; };
-
 __device__ __forceinline__ bool bb_overlap(double4 a, double4 b)
 {
     return (a.x <= b.z && b.x <= a.z && a.y <= b.w && b.y <= a.w);
@@ -236,16 +226,6 @@ __device__ __forceinline__ void world_from_pose(const DevParams &P, const EnvCtx
     const double tp = half_max(valid ? vy : -BP_INF);
     const double rad = gE(E.prop, i).x;
     outbb.x = l - rad; outbb.y = bo - rad; outbb.z = r + rad; outbb.w = tp + rad;
-}
-
-__device__ __forceinline__ void apply_contact_impulses(const ArbReg &A, int c, d2 &va, double &wa, d2 &vb, double &wb, d2 j)
-{
-    const d2 r1 = c ? A.r1_1 : A.r1_0, r2 = c ? A.r2_1 : A.r2_0;
-    const d2 jn = vneg(j);
-    va = vadd(va, vmul(jn, A.ma));
-    wa += A.ia * vcross(r1, jn);
-    vb = vadd(vb, vmul(j, A.mb));
-    wb += A.ib * vcross(r2, j);
 }
 
 // Support queries: for each of the nq records in L.q_dir / L.q_meta (direction d, body | vertex count << 16) the minimum of d . v over the body's
@@ -779,9 +759,7 @@ __device__ __forceinline__ void substep(const DevParams &P, const EnvCtx &E, con
                 if ((nB == 2 || cm >= om + BP_SUPPORT_MARGIN) && !BP_DBGP(8)) { i1B = (c0 > c1) ? iB0 : (c1 > c0) ? iB : min(iB0, iB); needB = false; }
             }
             // the winners of both sides are the next sub-step's cached planes
-            const unsigned long long nh = (unsigned long long)((unsigned)iA | ((unsigned)iB << 5) | ((unsigned)jA << 10) | ((unsigned)jB << 15) |
-                                                               ((unsigned)nA << 20) | ((unsigned)nB << 25)) |
-                                          HW_HAS_A | HW_HAS_B | (useA ? 0ull : HW_PRIM_B) | ((smax > rsum) ? 0ull : HW_BOTH);
+            const unsigned long long nh = hint_word(iA, iB, jA, jB, nA, nB, useA, smax, rsum);
             gE(E.hint, i * BP_KADJ + s) = nh;
             if (base == 0) L.cc_hw[lane] = nh;
         }
@@ -904,28 +882,10 @@ __device__ __forceinline__ void substep(const DevParams &P, const EnvCtx &E, con
                 const unsigned mh0 = (unsigned)__double2hiint(mh.x), mh1 = (unsigned)__double2hiint(mh.y);
                 const int mcount = __double2loint(mh.x);
                 if (BP_UNLIKELY2(fresh)) { // masses and material products of a pair stay with its arbiter
-                    A.state = ARB_FIRST; A.count = 0; A.h0 = A.h1 = 0; A.jn0 = A.jt0 = A.jn1 = A.jt1 = 0.0;
                     const int usa = (int)(A.key >> 16), usb = (int)(A.key & 0xFFFFu);
-                    const double4 m1 = gE(E.mass, usa), m2 = gE(E.mass, usb);
-                    A.ma = m1.x; A.ia = m1.y; A.mb = m2.x; A.ib = m2.y;
-                    const double4 q1 = gE(E.prop, usa), q2 = gE(E.prop, usb);
-                    A.e = q1.y * q2.y; A.u = q1.z * q2.z;
+                    arbiter_adopt(A, gE(E.mass, usa), gE(E.mass, usb), gE(E.prop, usa), gE(E.prop, usb));
                 }
-                double njn0 = 0.0, njt0 = 0.0, njn1 = 0.0, njt1 = 0.0;
-                if (A.count > 0 && A.h0 == mh0) { njn0 = A.jn0; njt0 = A.jt0; }
-                if (A.count > 1 && A.h1 == mh0) { njn0 = A.jn1; njt0 = A.jt1; }
-                if (mcount > 1) {
-                    if (A.count > 0 && A.h0 == mh1) { njn1 = A.jn0; njt1 = A.jt0; }
-                    if (A.count > 1 && A.h1 == mh1) { njn1 = A.jn1; njt1 = A.jt1; }
-                }
-                A.jn0 = njn0; A.jt0 = njt0; A.jn1 = njn1; A.jt1 = njt1;
-                A.h0 = mh0; A.h1 = mh1;
-                A.r1_0 = vsub(mp10, pa); A.r2_0 = vsub(mp20, pbp);
-                A.r1_1 = vsub(mp11, pa); A.r2_1 = vsub(mp21, pbp);
-                A.count = mcount;
-                A.n = mn_;
-                if (A.state == ARB_CACHED) A.state = ARB_FIRST;
-                A.stamp = now;
+                arbiter_update(A, mn_, mp10, mp20, mp11, mp21, mh0, mh1, mcount, pa, pbp, now);
             }
             lds_sync();
         }
@@ -983,11 +943,7 @@ __device__ __forceinline__ void substep(const DevParams &P, const EnvCtx &E, con
         }
     }
     // ---- 5. cpSpaceArbiterSetFilter ---------------------------------------------------------------------------
-    if (A.key != ARB_FREE_KEY) {
-        const unsigned ticks = now - A.stamp;
-        if (ticks >= 1u && A.state != ARB_CACHED) A.state = ARB_CACHED;
-        if (ticks >= (unsigned)P.persistence) A.key = ARB_FREE_KEY;
-    }
+    arbiter_filter(A, now, P.persistence);
     const bool active = (A.key != ARB_FREE_KEY) && (A.stamp == now);
     const unsigned long long amask = ballot(active);
     const int ba = (int)(A.key >> 16), bbi = (int)(A.key & 0xFFFFu);
@@ -1010,30 +966,9 @@ __device__ __forceinline__ void substep(const DevParams &P, const EnvCtx &E, con
         const d2 n = A.n;
         const d2 body_delta = vsub(pb, pa);
         const d2 t = vperp(n);
-        {
-            const double rcn1 = vcross(A.r1_0, n), rcn2 = vcross(A.r2_0, n);
-            nMass0 = 1.0 / ((A.ma + A.ia * rcn1 * rcn1) + (A.mb + A.ib * rcn2 * rcn2));
-            const double rct1 = vcross(A.r1_0, t), rct2 = vcross(A.r2_0, t);
-            tMass0 = 1.0 / ((A.ma + A.ia * rct1 * rct1) + (A.mb + A.ib * rct2 * rct2));
-            const double dist = vdot(vadd(vsub(A.r2_0, A.r1_0), body_delta), n);
-            bias0 = -P.bias_coef * fmin(0.0, dist + P.slop);   // divided by dt below when it is not a zero (a signed zero / dt is that zero)
-            jBias0 = 0.0;
-            const d2 v1 = vadd(va, vmul(vperp(A.r1_0), wa));
-            const d2 v2 = vadd(vb, vmul(vperp(A.r2_0), wb));
-            bounce0 = vdot(vsub(v2, v1), n) * A.e;
-        }
-        if (A.count > 1) {
-            const double rcn1 = vcross(A.r1_1, n), rcn2 = vcross(A.r2_1, n);
-            nMass1 = 1.0 / ((A.ma + A.ia * rcn1 * rcn1) + (A.mb + A.ib * rcn2 * rcn2));
-            const double rct1 = vcross(A.r1_1, t), rct2 = vcross(A.r2_1, t);
-            tMass1 = 1.0 / ((A.ma + A.ia * rct1 * rct1) + (A.mb + A.ib * rct2 * rct2));
-            const double dist = vdot(vadd(vsub(A.r2_1, A.r1_1), body_delta), n);
-            bias1 = -P.bias_coef * fmin(0.0, dist + P.slop);
-            jBias1 = 0.0;
-            const d2 v1 = vadd(va, vmul(vperp(A.r1_1), wa));
-            const d2 v2 = vadd(vb, vmul(vperp(A.r2_1), wb));
-            bounce1 = vdot(vsub(v2, v1), n) * A.e;
-        }
+        // bias0 / bias1 come back times dt: divided by dt below when they are not zeros (a signed zero / dt is that zero)
+        prestep_contact(P, A, A.r1_0, A.r2_0, n, t, body_delta, va, vb, wa, wb, nMass0, tMass0, bias0, jBias0, bounce0);
+        if (A.count > 1) prestep_contact(P, A, A.r1_1, A.r2_1, n, t, body_delta, va, vb, wa, wb, nMass1, tMass1, bias1, jBias1, bounce1);
     }
     // the bias velocity -bias_coef * min(0, dist + slop) / dt is a signed zero unless a contact is deeper than the slop: the two divisions run only then
     if (ballot(active && (bias0 != 0.0 || bias1 != 0.0))) { bias0 = bias0 / dt; bias1 = bias1 / dt; }
@@ -1305,10 +1240,9 @@ __device__ __forceinline__ void substep(const DevParams &P, const EnvCtx &E, con
     if (!AB && KIND != BP_ENV_BOX && (lvlmask & (lvlmask - 1u)) == 0u && lvlmask != 0u) {
         d2 va = mk2(0.0, 0.0), vb = va, wa2 = va, wb2 = va, vba = va, vbb = va;
         if (solve) gather(va, vb, wa2, wb2, vba, vbb);
-        auto negzero = [](double x) { return (((unsigned)__double2hiint(x) ^ 0x80000000u) | (unsigned)__double2loint(x)) == 0u; };
         bool nz = false;
-        if (solve && A.ma == 0.0) nz = negzero(va.x) || negzero(va.y) || negzero(wa2.x) || (AB && (negzero(wa2.y) || negzero(vba.x) || negzero(vba.y)));
-        if (solve && A.mb == 0.0) nz = nz || negzero(vb.x) || negzero(vb.y) || negzero(wb2.x) || (AB && (negzero(wb2.y) || negzero(vbb.x) || negzero(vbb.y)));
+        if (solve && A.ma == 0.0) nz = is_negzero(va.x) || is_negzero(va.y) || is_negzero(wa2.x) || (AB && (is_negzero(wa2.y) || is_negzero(vba.x) || is_negzero(vba.y)));
+        if (solve && A.mb == 0.0) nz = nz || is_negzero(vb.x) || is_negzero(vb.y) || is_negzero(wb2.x) || (AB && (is_negzero(wb2.y) || is_negzero(vbb.x) || is_negzero(vbb.y)));
         if (!ballot(nz)) {
             for (int it = 0; it < P.iterations; it++) {
                 PROF_CNT(42, 1)

@@ -640,9 +640,7 @@ __device__ __forceinline__ void substep_pair(const DevParams &P, const DevPtrs &
                 const double cmx = (c0 > c1) ? c0 : c1, om = (o0 > o1) ? o0 : o1;
                 if (nB == 2 || cmx >= om + BP_SUPPORT_MARGIN) { i1B = (c0 > c1) ? iB0 : (c1 > c0) ? iB : min(iB0, iB); needB = false; }
             }
-            const unsigned long long nh = (unsigned long long)((unsigned)iA | ((unsigned)iB << 5) | ((unsigned)jA << 10) | ((unsigned)jB << 15) |
-                                                               ((unsigned)nA << 20) | ((unsigned)nB << 25)) |
-                                          HW_HAS_A | HW_HAS_B | (useA ? 0ull : HW_PRIM_B) | ((smax > rsum) ? 0ull : HW_BOTH);
+            const unsigned long long nh = hint_word(iA, iB, jA, jB, nA, nB, useA, smax, rsum);
             gA(D.hint, (eo + i) * BP_KADJ + s) = nh;
             if (incache) Lcc_hw[base + hl] = nh;
         }
@@ -737,28 +735,10 @@ __device__ __forceinline__ void substep_pair(const DevParams &P, const DevPtrs &
                 const unsigned mh0 = (unsigned)__double2hiint(mh.x), mh1 = (unsigned)__double2hiint(mh.y);
                 const int mcount = __double2loint(mh.x);
                 if (BP_UNLIKELY2(fresh)) {
-                    A.state = ARB_FIRST; A.count = 0; A.h0 = A.h1 = 0; A.jn0 = A.jt0 = A.jn1 = A.jt1 = 0.0;
                     const int usa = (int)(A.key >> 16), usb = (int)(A.key & 0xFFFFu);
-                    const double4 m1 = gA(D.sc_mass, to + usa), m2 = gA(D.sc_mass, to + usb);
-                    A.ma = m1.x; A.ia = m1.y; A.mb = m2.x; A.ib = m2.y;
-                    const double4 q1 = gA(D.sc_prop, to + usa), q2 = gA(D.sc_prop, to + usb);
-                    A.e = q1.y * q2.y; A.u = q1.z * q2.z;
+                    arbiter_adopt(A, gA(D.sc_mass, to + usa), gA(D.sc_mass, to + usb), gA(D.sc_prop, to + usa), gA(D.sc_prop, to + usb));
                 }
-                double njn0 = 0.0, njt0 = 0.0, njn1 = 0.0, njt1 = 0.0;
-                if (A.count > 0 && A.h0 == mh0) { njn0 = A.jn0; njt0 = A.jt0; }
-                if (A.count > 1 && A.h1 == mh0) { njn0 = A.jn1; njt0 = A.jt1; }
-                if (mcount > 1) {
-                    if (A.count > 0 && A.h0 == mh1) { njn1 = A.jn0; njt1 = A.jt0; }
-                    if (A.count > 1 && A.h1 == mh1) { njn1 = A.jn1; njt1 = A.jt1; }
-                }
-                A.jn0 = njn0; A.jt0 = njt0; A.jn1 = njn1; A.jt1 = njt1;
-                A.h0 = mh0; A.h1 = mh1;
-                A.r1_0 = vsub(mp10, pa); A.r2_0 = vsub(mp20, pbp);
-                A.r1_1 = vsub(mp11, pa); A.r2_1 = vsub(mp21, pbp);
-                A.count = mcount;
-                A.n = mn_;
-                if (A.state == ARB_CACHED) A.state = ARB_FIRST;
-                A.stamp = now;
+                arbiter_update(A, mn_, mp10, mp20, mp11, mp21, mh0, mh1, mcount, pa, pbp, now);
             }
             lds_sync();
         }
@@ -771,11 +751,7 @@ __device__ __forceinline__ void substep_pair(const DevParams &P, const DevPtrs &
         if (Lmvs[a] != nowr && Lmvs[b] != nowr) A.stamp = now;
     }
     // ---- 5. cpSpaceArbiterSetFilter ---------------------------------------------------------------------------
-    if (A.key != ARB_FREE_KEY) {
-        const unsigned ticks = now - A.stamp;
-        if (ticks >= 1u && A.state != ARB_CACHED) A.state = ARB_CACHED;
-        if (ticks >= (unsigned)P.persistence) A.key = ARB_FREE_KEY;
-    }
+    arbiter_filter(A, now, P.persistence);
     const bool active = (A.key != ARB_FREE_KEY) && (A.stamp == now);
     const unsigned amask = hballot(active, h);
     S.nkeys = __popc(hballot(A.key != ARB_FREE_KEY, h));
@@ -792,30 +768,8 @@ __device__ __forceinline__ void substep_pair(const DevParams &P, const DevPtrs &
         const d2 n = A.n;
         const d2 body_delta = vsub(pb, pa);
         const d2 t = vperp(n);
-        {
-            const double rcn1 = vcross(A.r1_0, n), rcn2 = vcross(A.r2_0, n);
-            nMass0 = 1.0 / ((A.ma + A.ia * rcn1 * rcn1) + (A.mb + A.ib * rcn2 * rcn2));
-            const double rct1 = vcross(A.r1_0, t), rct2 = vcross(A.r2_0, t);
-            tMass0 = 1.0 / ((A.ma + A.ia * rct1 * rct1) + (A.mb + A.ib * rct2 * rct2));
-            const double dist = vdot(vadd(vsub(A.r2_0, A.r1_0), body_delta), n);
-            bias0 = -P.bias_coef * fmin(0.0, dist + P.slop);
-            jBias0 = 0.0;
-            const d2 v1 = vadd(va, vmul(vperp(A.r1_0), wa));
-            const d2 v2 = vadd(vb, vmul(vperp(A.r2_0), wb));
-            bounce0 = vdot(vsub(v2, v1), n) * A.e;
-        }
-        if (A.count > 1) {
-            const double rcn1 = vcross(A.r1_1, n), rcn2 = vcross(A.r2_1, n);
-            nMass1 = 1.0 / ((A.ma + A.ia * rcn1 * rcn1) + (A.mb + A.ib * rcn2 * rcn2));
-            const double rct1 = vcross(A.r1_1, t), rct2 = vcross(A.r2_1, t);
-            tMass1 = 1.0 / ((A.ma + A.ia * rct1 * rct1) + (A.mb + A.ib * rct2 * rct2));
-            const double dist = vdot(vadd(vsub(A.r2_1, A.r1_1), body_delta), n);
-            bias1 = -P.bias_coef * fmin(0.0, dist + P.slop);
-            jBias1 = 0.0;
-            const d2 v1 = vadd(va, vmul(vperp(A.r1_1), wa));
-            const d2 v2 = vadd(vb, vmul(vperp(A.r2_1), wb));
-            bounce1 = vdot(vsub(v2, v1), n) * A.e;
-        }
+        prestep_contact(P, A, A.r1_0, A.r2_0, n, t, body_delta, va, vb, wa, wb, nMass0, tMass0, bias0, jBias0, bounce0);
+        if (A.count > 1) prestep_contact(P, A, A.r1_1, A.r2_1, n, t, body_delta, va, vb, wa, wb, nMass1, tMass1, bias1, jBias1, bounce1);
     }
     // the division by dt changes nothing for a signed zero, so it runs for the whole wave as soon as one lane of either half has a bias term
     if (__ballot(active && (bias0 != 0.0 || bias1 != 0.0))) { bias0 = bias0 / dt; bias1 = bias1 / dt; }
@@ -998,10 +952,9 @@ __device__ __forceinline__ void substep_pair(const DevParams &P, const DevPtrs &
         if (!AB && __ballot((lvlmask & (lvlmask - 1u)) != 0u) == 0ull) {
             d2 va = mk2(0.0, 0.0), vb = va, wa2 = va, wb2 = va, vba = va, vbb = va;
             if (warm) gather(va, vb, wa2, wb2, vba, vbb);
-            auto negzero = [](double x) { return (((unsigned)__double2hiint(x) ^ 0x80000000u) | (unsigned)__double2loint(x)) == 0u; };
             bool nz = false;
-            if (warm && A.ma == 0.0) nz = negzero(va.x) || negzero(va.y) || negzero(wa2.x);
-            if (warm && A.mb == 0.0) nz = nz || negzero(vb.x) || negzero(vb.y) || negzero(wb2.x);
+            if (warm && A.ma == 0.0) nz = is_negzero(va.x) || is_negzero(va.y) || is_negzero(wa2.x);
+            if (warm && A.mb == 0.0) nz = nz || is_negzero(vb.x) || is_negzero(vb.y) || is_negzero(wb2.x);
             if (!__ballot(nz)) {
                 bool going1 = lvlmask != 0u;
                 for (int it = 0; it < P.iterations; it++) {

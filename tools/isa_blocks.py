@@ -10,11 +10,11 @@ import re
 import sys
 
 # phases of substep() as line ranges of csrc/bp_physics.hpp (update when the file moves; `grep -n "// ---- " csrc/bp_physics.hpp`)
-PH = [(291, 307, '0head'), (308, 381, '1integrate'), (382, 395, '2refresh'), (396, 480, '3candidates'), (481, 530, '4a_cached_planes'),
-      (531, 689, '4a_bound_rounds+search'), (690, 861, '4b_manifold'), (862, 983, '4c_deliver'), (984, 1000, '5events+filter'),
-      (1001, 1038, '6a_prestep'), (1039, 1066, '6a_warmset'), (1067, 1106, '6a_colour'), (1107, 1132, '6b_velint'), (1133, 1156, '6c_warmstart'),
-      (1157, 1282, '6d_solver'), (1283, 1337, '7post'), (1338, 1404, '7mvlist'), (256, 280, 'support_queries'), (216, 238, 'world_from_pose'),
-      (163, 213, 'refresh_body')]
+PH = [(272, 288, '0head'), (289, 362, '1integrate'), (363, 376, '2refresh'), (377, 461, '3candidates'), (462, 511, '4a_cached_planes'),
+      (512, 670, '4a_bound_rounds+search'), (671, 840, '4b_manifold'), (841, 944, '4c_deliver'), (945, 957, '5events+filter'),
+      (958, 974, '6a_prestep'), (975, 1002, '6a_warmset'), (1003, 1042, '6a_colour'), (1043, 1068, '6b_velint'), (1069, 1092, '6c_warmstart'),
+      (1093, 1280, '6d_solver'), (1281, 1335, '7post'), (1336, 1402, '7mvlist'), (237, 261, 'support_queries'), (207, 229, 'world_from_pose'),
+      (154, 204, 'refresh_body')]
 
 
 def phase_of(chain):

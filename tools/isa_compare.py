@@ -2,7 +2,9 @@
 flags plus -save-temps (gfx950 device assembly), then compares, for every kernel symbol of the first tree, the metadata fields below and the
 instruction count (lines between the kernel's label and its .Lfunc_end that are neither labels, directives nor comments).
 
-    python tools/isa_compare.py <parent tree> <branch tree> [--out report.txt]
+    python tools/isa_compare.py <parent tree> <branch tree> [--out report.txt] [--define NAME[=V]]...
+
+--define appends -DNAME[=V] to both builds, so the diagnostic twins (BP_DEBUG_PATHS=1, BP_PROF=1) compare the same way.
 
 Exit status 1 if any kernel of the parent differs or is missing on the branch.  Kernels that exist only on the branch are listed.
 """
@@ -19,10 +21,10 @@ FIELDS = [".vgpr_count", ".sgpr_count", ".vgpr_spill_count", ".sgpr_spill_count"
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared", "-std=c++17", "-Wno-unused-value"]
 
 
-def device_asm(tree, work):
+def device_asm(tree, work, defines=()):
     src = os.path.join(os.path.abspath(tree), "benchpush_amd", "csrc", "bp_capi.hip")
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    subprocess.check_call([hipcc] + FLAGS + ["-save-temps", "-o", os.path.join(work, "lib.so"), src], cwd=work)
+    subprocess.check_call([hipcc] + FLAGS + ["-D" + d for d in defines] + ["-save-temps", "-o", os.path.join(work, "lib.so"), src], cwd=work)
     s = [p for p in glob.glob(os.path.join(work, "*.s")) if "gfx950" in p]
     if len(s) != 1:
         raise SystemExit("expected one gfx950 assembly file in %s, found %s" % (work, s))
@@ -67,9 +69,10 @@ def main():
     ap.add_argument("parent")
     ap.add_argument("branch")
     ap.add_argument("--out")
+    ap.add_argument("--define", action="append", default=[], metavar="NAME[=V]")
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as w0, tempfile.TemporaryDirectory() as w1:
-        k0, k1 = kernels(device_asm(a.parent, w0)), kernels(device_asm(a.branch, w1))
+        k0, k1 = kernels(device_asm(a.parent, w0, a.define)), kernels(device_asm(a.branch, w1, a.define))
     rows, bad = [], 0
     keys = FIELDS + ["insts"]
     for name in sorted(k0):
