@@ -29,7 +29,10 @@ EXPORTS = ["bp_abi_version", "bp_create", "bp_destroy", "bp_load_scenarios", "bp
            "bp_device_shared", "bp_launch_policy_query", "bp_bd_budget", "bp_get_cost_stats", "bp_bd_get_cycle_skips",
            "bp_sizeof_render_args", "bp_sizeof_render_prim", "bp_set_render_table", "bp_render",
            "bp_state_bytes", "bp_state_layout_id", "bp_save_state", "bp_load_state", "bp_clone_state", "bp_state_layout_query",
-           "bp_sizeof_swath_config", "bp_swath_cost"]
+           "bp_sizeof_swath_config", "bp_swath_cost",
+           "bp_sizeof_lattice_config", "bp_lattice_workspace_bytes", "bp_lattice_search"]
+LATTICE_FOUND, LATTICE_NO_PATH, LATTICE_CAP, LATTICE_SKIPPED = 0, 1, 2, 3
+LATTICE_MAX_EDGES = 32   # bp_lattice_search: edges per base heading at most
 SWATH_CLIP, SWATH_REJECT = 0, 1
 SWATH_MAX_WORDS = 4096   # bp_swath_cost: H * ceil(W / 64) at most (the swath's bit image lives in LDS)
 STATE_TRUSTED = 1    # BP_STATE_TRUSTED: bp_load_state / bp_clone_state skip the argument checks and the synchronisation
@@ -43,6 +46,13 @@ class BpCostmapConfig(C.Structure):
 class BpSwathConfig(C.Structure):
     _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("K", C.c_int32), ("P", C.c_int32), ("nv", C.c_int32), ("outside", C.c_int32),
                 ("map_stride", C.c_int64)]
+
+
+class BpLatticeConfig(C.Structure):
+    _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("S", C.c_int32), ("nh", C.c_int32), ("nb", C.c_int32), ("ne_max", C.c_int32), ("den", C.c_int32),
+                ("margin", C.c_int32), ("h_baseline", C.c_int32), ("max_expansions", C.c_int32), ("node_capacity", C.c_int32),
+                ("queue_capacity", C.c_int32), ("max_path_nodes", C.c_int32), ("pad_", C.c_int32), ("map_stride", C.c_int64),
+                ("mask_stride", C.c_int64), ("unit", C.c_double), ("weight", C.c_double), ("turning_radius", C.c_double)]
 
 
 class BpConfig(C.Structure):
@@ -197,6 +207,13 @@ def load():
         if L.bp_sizeof_swath_config() != C.sizeof(BpSwathConfig):
             raise BpError("bp_swath_config layout mismatch between _lib.BpSwathConfig and the library")
         L.bp_swath_cost.argtypes = [vp, C.POINTER(BpSwathConfig), vp, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "bp_lattice_search"):   # lattice A* (absent from older builds loaded for same-box comparisons)
+        L.bp_sizeof_lattice_config.restype = C.c_int32
+        if L.bp_sizeof_lattice_config() != C.sizeof(BpLatticeConfig):
+            raise BpError("bp_lattice_config layout mismatch between _lib.BpLatticeConfig and the library")
+        L.bp_lattice_workspace_bytes.argtypes = [C.POINTER(BpLatticeConfig), C.c_int32]
+        L.bp_lattice_workspace_bytes.restype = C.c_int64
+        L.bp_lattice_search.argtypes = [vp, C.POINTER(BpLatticeConfig)] + [vp] * 10 + [C.c_int64] + [vp] * 7
     _lib = L
     return L
 

@@ -22,6 +22,7 @@
 #include "bp_render.hpp"
 #include "bp_state.hpp"
 #include "bp_swath.hpp"
+#include "bp_lattice.hpp"
 
 struct bp_handle {
     bp_config cfg;
@@ -1356,6 +1357,82 @@ int bp_swath_cost(bp_handle *h, const bp_swath_config *cfg, const double *cost_m
     A.map_stride = cfg->map_stride;
     A.maps = cost_maps; A.paths = paths; A.fp = footprint; A.lengths = lengths; A.rows = rows; A.costs = costs; A.swaths = swaths;
     hipLaunchKernelGGL(k_swath_cost, dim3((unsigned)ncand), dim3(64), (size_t)words * 8, (hipStream_t)stream, A);
+    HIPCHK(h, hipGetLastError());
+    return BP_OK;
+}
+// ---- lattice A* ----
+struct LatLayout { long long hcap, off_nodes, off_heap, per_env; };
+static bool lattice_layout(const bp_lattice_config *c, LatLayout &L)
+{
+    if (!c || c->node_capacity <= 0 || c->queue_capacity <= 0 || c->node_capacity > (1 << 24) || c->queue_capacity > (1 << 26)) return false;
+    long long hc = 64;
+    while (hc < 2ll * c->node_capacity) hc <<= 1;
+    L.hcap = hc;
+    L.off_nodes = hc * 4;
+    L.off_heap = (L.off_nodes + (long long)c->node_capacity * (long long)sizeof(LatNode) + 15) & ~15ll;
+    L.per_env = L.off_heap + (long long)c->queue_capacity * (long long)sizeof(LatEntry);
+    return true;
+}
+int32_t bp_sizeof_lattice_config(void) { return (int32_t)sizeof(bp_lattice_config); }
+int64_t bp_lattice_workspace_bytes(const bp_lattice_config *cfg, int32_t num_envs)
+{
+    LatLayout L;
+    if (num_envs <= 0 || !lattice_layout(cfg, L)) return BP_EINVAL;
+    return (int64_t)(L.per_env * num_envs);
+}
+int bp_lattice_search(bp_handle *h, const bp_lattice_config *cfg, const double *cost_maps, const double *starts, const double *goal_y, const uint8_t *active,
+                      const double *edges_host, const int32_t *edge_headings_host, const double *edge_lengths_host, const int32_t *edge_counts_host,
+                      const uint64_t *masks, void *workspace, int64_t workspace_bytes, int32_t *status, double *g, int32_t *expanded, int32_t *n_nodes,
+                      double *nodes, int32_t *edges, void *stream)
+{
+    if (!h || !cfg || !cost_maps || !starts || !goal_y || !edges_host || !edge_headings_host || !edge_lengths_host || !edge_counts_host || !masks ||
+        !workspace || !status || !g || !expanded || !n_nodes || !nodes || !edges) return BP_EINVAL;
+    if (!h->loaded || !h->was_reset) return fail(h, BP_ESTATE, "bp_lattice_search before bp_load_scenarios/bp_reset");
+    if (h->P.env_kind != BP_ENV_SHIP_ICE) return fail(h, BP_EINVAL, "bp_lattice_search: ship-ice handles only");
+    if (cfg->H <= 0 || cfg->W <= 0) return fail(h, BP_EINVAL, "bp_lattice_search: H and W must be positive");
+    if (cfg->S <= 0 || cfg->S > 64 || (cfg->S & 1) == 0) return fail(h, BP_EINVAL, "bp_lattice_search: mask side S must be odd and at most 64 (one mask row per lane)");
+    if ((cfg->nh != 8 && cfg->nh != 16) || cfg->nb * 4 != cfg->nh) return fail(h, BP_EINVAL, "bp_lattice_search: 8 or 16 headings, nb = nh / 4");
+    if (cfg->ne_max <= 0 || cfg->ne_max > BP_LAT_MAX_EDGES) return fail(h, BP_EINVAL, "bp_lattice_search: 1 .. 32 edges per base heading");
+    if (cfg->den <= 0 || cfg->den > 64 || !(cfg->unit > 0.0) || !std::isfinite(cfg->unit) || cfg->margin < 0 || !std::isfinite(cfg->weight) ||
+        !(cfg->turning_radius > 0.0) || !std::isfinite(cfg->turning_radius))
+        return fail(h, BP_EINVAL, "bp_lattice_search: den, unit, margin, weight or turning_radius out of range");
+    if (cfg->max_expansions <= 0 || cfg->node_capacity <= 0 || cfg->queue_capacity <= 0 || cfg->max_path_nodes <= 0)
+        return fail(h, BP_EINVAL, "bp_lattice_search: the caps must be positive");
+    LatLayout L;
+    if (!lattice_layout(cfg, L)) return fail(h, BP_EINVAL, "bp_lattice_search: node_capacity above 2^24 or queue_capacity above 2^26");
+    const long long cells = (long long)cfg->H * cfg->W, mwords = (long long)cfg->nh * cfg->ne_max * cfg->S;
+    if (cfg->map_stride < 0 || (cfg->map_stride > 0 && cfg->map_stride < cells)) return fail(h, BP_EINVAL, "bp_lattice_search: bad map_stride");
+    if (cfg->mask_stride < 0 || (cfg->mask_stride > 0 && cfg->mask_stride < mwords)) return fail(h, BP_EINVAL, "bp_lattice_search: bad mask_stride");
+    const double u = cfg->unit / (double)cfg->den;
+    if (!(std::hypot((double)cfg->H, (double)cfg->W) / u < (double)(BP_LAT_KEY_OFF - 2)))
+        return fail(h, BP_EINVAL, "bp_lattice_search: the map's diagonal exceeds 4094 sub-units");
+    if (workspace_bytes < L.per_env * (long long)h->num_envs || (((uintptr_t)workspace) & 15u))
+        return fail(h, BP_EINVAL, "bp_lattice_search: workspace smaller than bp_lattice_workspace_bytes or not 16-byte aligned");
+    LatticeArgs A;
+    memset(&A, 0, sizeof(A));
+    for (int b = 0; b < cfg->nb; b++) {
+        const int ne = edge_counts_host[b];
+        if (ne <= 0 || ne > cfg->ne_max) return fail(h, BP_EINVAL, "bp_lattice_search: edge count outside 1 .. ne_max");
+        A.ne[b] = ne;
+        for (int k = 0; k < ne; k++) {
+            const size_t s = (size_t)b * cfg->ne_max + k;
+            const int t = b * BP_LAT_MAX_EDGES + k;
+            const double ex = edges_host[2 * s] * cfg->den, ey = edges_host[2 * s + 1] * cfg->den;
+            if (!(std::fabs(ex) <= 1024.0 && std::fabs(ey) <= 1024.0) || ex != std::nearbyint(ex) || ey != std::nearbyint(ey))
+                return fail(h, BP_EINVAL, "bp_lattice_search: an edge is not a multiple of the sub-unit (unit / den)");
+            if (edge_headings_host[s] < 0 || edge_headings_host[s] >= cfg->nh) return fail(h, BP_EINVAL, "bp_lattice_search: edge heading outside [0, nh)");
+            A.ex[t] = (short)ex; A.ey[t] = (short)ey; A.eh[t] = (signed char)edge_headings_host[s]; A.len[t] = edge_lengths_host[s];
+        }
+    }
+    BP_DEVICE(h);
+    A.H = cfg->H; A.W = cfg->W; A.S = cfg->S; A.mv = cfg->S / 2; A.nh = cfg->nh; A.nb = cfg->nb; A.ne_max = cfg->ne_max; A.margin = cfg->margin;
+    A.h_baseline = cfg->h_baseline != 0; A.max_exp = cfg->max_expansions; A.ncap = cfg->node_capacity; A.hcap = (int)L.hcap; A.qcap = cfg->queue_capacity;
+    A.nmax = cfg->max_path_nodes; A.map_stride = cfg->map_stride; A.mask_stride = cfg->mask_stride;
+    A.ws_stride = (unsigned long long)L.per_env; A.off_nodes = (unsigned long long)L.off_nodes; A.off_heap = (unsigned long long)L.off_heap;
+    A.u = u; A.weight = cfg->weight; A.r = cfg->turning_radius;
+    A.maps = cost_maps; A.starts = starts; A.goal_y = goal_y; A.active = active; A.masks = (const unsigned long long *)masks; A.ws = (unsigned char *)workspace;
+    A.status = status; A.expanded = expanded; A.n_nodes = n_nodes; A.edges = edges; A.g = g; A.nodes = nodes;
+    hipLaunchKernelGGL(k_lattice_search, dim3((unsigned)h->num_envs), dim3(64), 0, (hipStream_t)stream, A);
     HIPCHK(h, hipGetLastError());
     return BP_OK;
 }

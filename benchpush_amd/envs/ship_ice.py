@@ -133,6 +133,14 @@ class _BatchedBase:
             t[d] = t[s]
 
 
+class LatticeResult:
+    """Device tensors of ``BatchedShipIceEnv.lattice_search``: status, g, expanded, n_nodes [E]; nodes [E, N, 3]; edges [E, N]."""
+    __slots__ = ("status", "g", "expanded", "n_nodes", "nodes", "edges")
+
+    def __init__(self, status, g, expanded, n_nodes, nodes, edges):
+        self.status, self.g, self.expanded, self.n_nodes, self.nodes, self.edges = status, g, expanded, n_nodes, nodes, edges
+
+
 class BatchedShipIceEnv(_BatchedBase):
     """E independent ship-ice environments on one GPU.
 
@@ -372,6 +380,81 @@ class BatchedShipIceEnv(_BatchedBase):
         _lib.check(self.L, self.h, self.L.bp_swath_cost(self.h, C.byref(cfg), _ptr(cost_maps), _ptr(paths), _ptr(lengths), _ptr(rows), _ptr(footprint),
                                                         _ptr(costs), _ptr(swaths) if return_swaths else None, self._stream()), "bp_swath_cost")
         return (costs, swaths) if return_swaths else costs
+
+    def lattice_search(self, cost_maps, starts, goal_y, prims, masks, weight=1.0, h_baseline=False, margin=None, active=None, max_expansions=8192,
+                       max_path_nodes=128, node_capacity=None, queue_capacity=None, out=None):
+        """Lattice A* of every env over the cost maps, on the device (bp_lattice_search): ``AStar.search`` of the reference's planning baseline for the
+        goal line y >= goal_y, one wavefront per env, no host synchronisation.  DESIGN.md "Lattice search" states the semantics.
+
+        cost_maps  float64 [E, H, W] (``cost_maps()``) or one shared [H, W] map
+        starts     float64 [E, 3] = (x, y, theta) in cells / radians; goal_y float64 [E] in cells
+        prims      ``planning.LatticePrimitives``; masks int64 [E, nh * ne_max, S] (``planning.lattice_swath_masks``) or one shared [nh * ne_max, S]
+        weight     f = g + weight * h; h_baseline: h = max(0, goal_y - y) instead of the Dubins heuristic; margin: rows below the start and above the goal
+                   that the window keeps (None: int(5 * prims.scale), the reference's default)
+        active     bool / uint8 [E] or None: envs with False are SKIPPED and only their status is written
+        max_expansions, max_path_nodes, node_capacity (None: 2 * max_expansions), queue_capacity (None: 2 * max_expansions): the caps; exceeding one
+                   gives status CAP.  profiles/lattice/README.md records what the shipped configuration needs.
+        out        None or a LatticeResult of a previous call with the same shapes, to be overwritten
+
+        Returns a LatticeResult of device tensors: status int32 [E] (LATTICE_FOUND 0, NO_PATH 1, CAP 2, SKIPPED 3), g float64 [E], expanded int32 [E],
+        n_nodes int32 [E], nodes float64 [E, max_path_nodes, 3] = (X, Y, world heading) start to goal, edges int32 [E, max_path_nodes] (base * ne_max + k,
+        -1 for the start).  Only rows 0 .. n_nodes-1 of found envs are written.  The workspace is cached on the env.  Raises ValueError, before any launch,
+        for a wrong dtype, device, shape or a non-contiguous tensor; BpError for what the library refuses.  Touches no environment state."""
+        E = self.num_envs
+
+        def need(t, name, dtypes, shapes):
+            dtypes = dtypes if isinstance(dtypes, tuple) else (dtypes,)
+            if not isinstance(t, torch.Tensor) or t.dtype not in dtypes or t.device != self.device or not t.is_contiguous():
+                raise ValueError("lattice_search: %s must be a contiguous %s tensor on %s" % (name, " / ".join(map(str, dtypes)), self.device))
+            if not any(len(sh) == t.dim() and all(a is None or a == b for a, b in zip(sh, t.shape)) for sh in shapes):
+                raise ValueError("lattice_search: %s has shape %s, expected %s" % (name, tuple(t.shape), " or ".join(str(list(sh)) for sh in shapes)))
+
+        nh, nb, nem = int(prims.num_headings), int(prims.num_base_h), int(prims.ne_max)
+        need(cost_maps, "cost_maps", torch.float64, [(E, None, None), (None, None)])
+        H, W = int(cost_maps.shape[-2]), int(cost_maps.shape[-1])
+        need(starts, "starts", torch.float64, [(E, 3)])
+        need(goal_y, "goal_y", torch.float64, [(E,)])
+        need(masks, "masks", torch.int64, [(E, nh * nem, None), (nh * nem, None)])
+        S = int(masks.shape[-1])
+        if active is not None:
+            need(active, "active", (torch.bool, torch.uint8), [(E,)])
+        if min(H, W, S) <= 0:
+            raise ValueError("lattice_search: empty cost maps or masks")
+        node_capacity = 2 * int(max_expansions) if node_capacity is None else int(node_capacity)
+        queue_capacity = 2 * int(max_expansions) if queue_capacity is None else int(queue_capacity)
+        N = int(max_path_nodes)
+        if out is None:
+            if N <= 0:
+                raise ValueError("lattice_search: max_path_nodes must be positive")
+            out = LatticeResult(torch.empty(E, dtype=torch.int32, device=self.device), torch.empty(E, dtype=torch.float64, device=self.device),
+                                torch.empty(E, dtype=torch.int32, device=self.device), torch.empty(E, dtype=torch.int32, device=self.device),
+                                torch.zeros((E, N, 3), dtype=torch.float64, device=self.device),
+                                torch.full((E, N), -1, dtype=torch.int32, device=self.device))
+        else:
+            need(out.status, "out.status", torch.int32, [(E,)])
+            need(out.g, "out.g", torch.float64, [(E,)])
+            need(out.expanded, "out.expanded", torch.int32, [(E,)])
+            need(out.n_nodes, "out.n_nodes", torch.int32, [(E,)])
+            need(out.nodes, "out.nodes", torch.float64, [(E, N, 3)])
+            need(out.edges, "out.edges", torch.int32, [(E, N)])
+        cfg = _lib.BpLatticeConfig(H=H, W=W, S=S, nh=nh, nb=nb, ne_max=nem, den=int(prims.den), margin=int(5 * prims.scale) if margin is None else int(margin),
+                                   h_baseline=int(bool(h_baseline)), max_expansions=int(max_expansions), node_capacity=node_capacity,
+                                   queue_capacity=queue_capacity, max_path_nodes=N, pad_=0, map_stride=H * W if cost_maps.dim() == 3 else 0,
+                                   mask_stride=nh * nem * S if masks.dim() == 3 else 0, unit=float(prims.scale), weight=float(weight),
+                                   turning_radius=float(prims.turning_radius))
+        nbytes = int(self.L.bp_lattice_workspace_bytes(C.byref(cfg), E))
+        ws = getattr(self, "_lattice_ws", None)
+        if nbytes > 0 and (ws is None or ws.numel() < nbytes):
+            ws = self._lattice_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        e, hd, ln, cnt = prims.tables()
+        e, hd, ln, cnt = (np.ascontiguousarray(e, np.float64), np.ascontiguousarray(hd, np.int32), np.ascontiguousarray(ln, np.float64),
+                          np.ascontiguousarray(cnt, np.int32))
+        hp = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+        _lib.check(self.L, self.h, self.L.bp_lattice_search(
+            self.h, C.byref(cfg), _ptr(cost_maps), _ptr(starts), _ptr(goal_y), _ptr(active) if active is not None else None, hp(e), hp(hd), hp(ln), hp(cnt),
+            _ptr(masks), _ptr(ws) if ws is not None else None, ws.numel() if ws is not None else 0, _ptr(out.status), _ptr(out.g), _ptr(out.expanded),
+            _ptr(out.n_nodes), _ptr(out.nodes), _ptr(out.edges), self._stream()), "bp_lattice_search")
+        return out
 
     def episode_metrics(self):
         """On-device ShipIceMetric: (rows [E, 6] float64 = efficiency, effort, episode reward, success, episode length, total_work of

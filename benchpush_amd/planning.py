@@ -1,13 +1,17 @@
 """Small helpers for planners that score candidate paths on the device with ``BatchedShipIceEnv.swath_costs``.
 
 Plain torch / numpy, not a hot path: the footprint of the reference's ``Ship`` (common/ship.py:18-20), constant-curvature candidate paths in closed
-form, and the replanning comparison of ``Path.update`` (common/utils/utils.py:58-89).  The lattice A* itself (Dubins primitives, pre-rotated swath
-dictionaries) is not ported.
+form, the replanning comparison of ``Path.update`` (common/utils/utils.py:58-89), and what the lattice A* (``BatchedShipIceEnv.lattice_search``)
+takes and gives: the primitive tables (``LatticePrimitives``, common/primitives.py), the swath masks (``lattice_swath_masks``, common/swath.py:15-88) and
+the sampled path of a search result (``lattice_full_paths``, ``AStar.build_path``).
 """
 import numpy as np
 import torch
 
-__all__ = ["ship_footprint", "arc_paths", "replan_mask", "LATTICE_SHIP_VERTICES"]
+from . import dubins as _dubins
+
+__all__ = ["ship_footprint", "arc_paths", "replan_mask", "LATTICE_SHIP_VERTICES", "LatticePrimitives", "ship_halves", "lattice_max_val",
+           "lattice_swath_masks", "lattice_full_paths"]
 
 # ship.vertices of the reference's lattice planner configuration (17 vertices, some collinear); with padding 0.25 and scale 5 it is the planner's footprint
 LATTICE_SHIP_VERTICES = [[1., -0.], [0.9, 0.10], [0.5, 0.25], [0.25, 0.25], [0, 0.25], [-0.25, 0.25], [-0.5, 0.25], [-0.75, 0.25], [-1., 0.25],
@@ -53,3 +57,193 @@ def replan_mask(new_cost, old_cost, threshold_cost=0.95):
     """The comparison of ``Path.update``: True where the new path's swath cost is below threshold_cost times the old path's (tensors or arrays of any
     equal shape; both costs taken over the same row window, ``swath_costs(rows=...)``)."""
     return new_cost < old_cost * threshold_cost
+
+
+class LatticePrimitives:
+    """The reference's ``Primitives`` (common/primitives.py) for a control set that the caller passes as data.
+
+    edge_sets       {(0, 0, b): [(x, y, heading), ...]} or a list indexed by the base heading b, in lattice units (``Primitives.get_primitives``)
+    num_headings    8 or 16; len(edge_sets) == num_headings / 4
+    scale           cells per lattice unit; turning_radius in lattice units; step_size in cells between the samples of a primitive's path
+
+    Attributes as in the reference: edge_set_dict (scaled edges), paths {((0, 0, b), edge): [3, P]}, path_lengths, num_base_h, max_prim, spacing,
+    turning_radius (cells).  Beside them the tables of the C ABI: edges [nb][k] unscaled, den (sub-units per lattice unit: the smallest integer that
+    makes every edge an integer), ne_max, and samples(b, k) / length(b, k)."""
+
+    def __init__(self, edge_sets, num_headings=8, scale=1.0, turning_radius=1.0, step_size=0.25, _paths=None):
+        sets = [edge_sets[(0, 0, b)] for b in range(len(edge_sets))] if isinstance(edge_sets, dict) else list(edge_sets)
+        self.num_headings, self.scale, self.step_size = int(num_headings), float(scale), float(step_size)
+        self.turning_radius = float(turning_radius) * self.scale
+        self.num_base_h = len(sets)
+        if self.num_headings not in (8, 16) or self.num_base_h * 4 != self.num_headings:
+            raise ValueError("LatticePrimitives: 8 or 16 headings with num_headings / 4 edge sets")
+        self.edges = [[(float(x), float(y), int(h)) for x, y, h in es] for es in sets]
+        self.ne_max = max(len(es) for es in self.edges)
+        self.den = next((d for d in range(1, 65) if all((x * d).is_integer() and (y * d).is_integer() for es in self.edges for x, y, _ in es)), None)
+        if self.den is None:
+            raise ValueError("LatticePrimitives: the edges share no sub-unit of 1/64 lattice unit or coarser")
+        self.spacing = 2 * np.pi / self.num_headings
+        self.edge_set_dict = {(0, 0, b): [(x * self.scale, y * self.scale, h) for x, y, h in es] for b, es in enumerate(self.edges)}
+        self.paths, self.path_lengths = {}, {}
+        for origin, es in self.edge_set_dict.items():
+            for edge in es:
+                if _paths is not None:
+                    self.paths[(origin, edge)], self.path_lengths[(origin, edge)] = _paths(origin, edge)
+                    continue
+                # get_points_on_dubins_path(p1=origin, p2=edge, initial_heading=0, eps=1e-10)
+                t0 = (origin[2] * 2 * np.pi / self.num_headings) % (2 * np.pi)
+                t1 = (edge[2] * 2 * np.pi / self.num_headings) % (2 * np.pi)
+                dp = _dubins.shortest_path((origin[0], origin[1], t0), (edge[0], edge[1], t1), self.turning_radius - 1e-10)
+                conf, _ = dp.sample_many(self.step_size)
+                self.paths[(origin, edge)] = np.asarray(conf, np.float64).T.reshape(3, -1)
+                self.path_lengths[(origin, edge)] = dp.path_length()
+        self.max_prim = int(round(max(self.path_lengths.values())))
+
+    @classmethod
+    def from_reference(cls, prim):
+        """From any object with the reference's attributes (edge_set_dict scaled, paths, path_lengths, num_headings, scale, turning_radius scaled,
+        step_size): its own paths and lengths are taken over, nothing is recomputed."""
+        nb = len(prim.edge_set_dict)
+        scale = float(prim.scale)
+        sets = [[(x / scale, y / scale, h) for x, y, h in prim.edge_set_dict[(0, 0, b)]] for b in range(nb)]
+        look = {}
+        for b in range(nb):
+            for k, e in enumerate(prim.edge_set_dict[(0, 0, b)]):
+                look[(b, k)] = (np.asarray(prim.paths[((0, 0, b), e)], np.float64), float(prim.path_lengths[((0, 0, b), e)]))
+        self = cls.__new__(cls)
+        order = iter([look[(b, k)] for b in range(nb) for k in range(len(sets[b]))])
+        cls.__init__(self, sets, prim.num_headings, scale, float(prim.turning_radius) / scale, prim.step_size, _paths=lambda o, e: next(order))
+        return self
+
+    def samples(self, b, k):
+        return self.paths[((0, 0, b), self.edge_set_dict[(0, 0, b)][k])]
+
+    def length(self, b, k):
+        return self.path_lengths[((0, 0, b), self.edge_set_dict[(0, 0, b)][k])]
+
+    def tables(self):
+        """(edges float64 [nb, ne_max, 2] in lattice units, headings int32 [nb, ne_max], lengths float64 [nb, ne_max] in cells, counts int32 [nb])."""
+        nb = self.num_base_h
+        e, hd, ln, cnt = np.zeros((nb, self.ne_max, 2)), np.zeros((nb, self.ne_max), np.int32), np.zeros((nb, self.ne_max)), np.zeros(nb, np.int32)
+        for b, es in enumerate(self.edges):
+            cnt[b] = len(es)
+            for k, (x, y, h) in enumerate(es):
+                e[b, k], hd[b, k], ln[b, k] = (x, y), h, self.length(b, k)
+        return e, hd, ln, cnt
+
+
+def _hull(points):
+    """Convex hull, counter-clockwise, collinear points dropped (monotone chain)."""
+    pts = sorted(set(map(tuple, np.asarray(points, np.float64).tolist())))
+    cross = lambda o, a, b: (a[0] - o[0]) * (b[1] - o[1]) - (a[1] - o[1]) * (b[0] - o[0])   # noqa: E731
+    lower, upper = [], []
+    for p in pts:
+        while len(lower) >= 2 and cross(lower[-2], lower[-1], p) <= 0:
+            lower.pop()
+        lower.append(p)
+    for p in reversed(pts):
+        while len(upper) >= 2 and cross(upper[-2], upper[-1], p) <= 0:
+            upper.pop()
+        upper.append(p)
+    return np.asarray(lower[:-1] + upper[:-1], np.float64)
+
+
+def ship_halves(footprint):
+    """``Ship.split_vertices`` (common/ship.py:110-131) widened as in ``generate_swath`` (common/swath.py:33-34): the convex hulls of the footprint's
+    x >= 0 and x <= 0 vertices plus (0, +-width / 2), every y grown by width / 2.  Returns (right, left) float64 [n, 2]."""
+    v = np.asarray(footprint, np.float64).reshape(-1, 2)
+    width = v[:, 1].max() - v[:, 1].min()
+    extra = np.array([[0.0, width / 2], [0.0, -width / 2]])
+    out = []
+    for half in (v[v[:, 0] >= 0], v[v[:, 0] <= 0]):
+        hv = _hull(np.concatenate((half, extra)))
+        out.append(np.stack([hv[:, 0], np.sign(hv[:, 1]) * (np.abs(hv[:, 1]) + width / 2)], 1))
+    return out[0], out[1]
+
+
+def lattice_max_val(prims, footprint):
+    """``AStar.max_val`` = int(max_prim + max_ship_length // 2): half the side of the swath masks, S = 2 * max_val + 1."""
+    v = np.asarray(footprint, np.float64).reshape(-1, 2)
+    d = np.sqrt(((v[:, None, :] - v[None, :, :]) ** 2).sum(-1)).max()
+    return int(prims.max_prim + int(np.ceil(d)) // 2)
+
+
+def lattice_swath_masks(env, prims, footprint, theta0):
+    """The swath masks of every (heading, edge) key for every env, rasterised on the device with no host synchronisation: int64 [E, nh * ne_max, S],
+    word r of key h * ne_max + k = row r of the S x S mask (bit c = column c) of edge k taken from a node of lattice heading h, the node at the centre
+    cell.  The footprint is swept along the primitive's samples rotated by theta0 + q * 90 deg (q = h // nb) with ``swath_costs(return_swaths=True)``
+    on a blank S x S map, then the two widened ship halves at the first sample are removed (``generate_swath``'s planning branch).  theta0: [E] tensor
+    or array in radians, taken mod 2 pi.  Unlike the reference, which rotates the theta0 = 0 raster with a nearest-neighbour image rotation, the rotated
+    primitive itself is rasterised (DESIGN.md "Lattice search")."""
+    E, dev = env.num_envs, env.device
+    nh, nb, nem = prims.num_headings, prims.num_base_h, prims.ne_max
+    mv = lattice_max_val(prims, footprint)
+    S = 2 * mv + 1
+    if S > 64:
+        raise ValueError("lattice_swath_masks: masks of %d cells per side exceed the 64 of bp_lattice_search" % S)
+    K = nh * nem
+    P = max(prims.samples(b, k).shape[1] for b in range(nb) for k in range(len(prims.edges[b])))
+    base = np.zeros((K, P, 3))
+    lens = np.zeros(K, np.int32)
+    quad = np.zeros(K)
+    for h in range(nh):
+        b, q = h % nb, h // nb
+        for k in range(len(prims.edges[b])):
+            sm = prims.samples(b, k)
+            base[h * nem + k, :sm.shape[1]] = sm.T
+            lens[h * nem + k] = sm.shape[1]
+            quad[h * nem + k] = q
+    th0 = torch.remainder(torch.as_tensor(theta0, dtype=torch.float64).to(dev).reshape(E), 2 * np.pi)
+    base_t = torch.from_numpy(base).to(dev)
+    rot = th0[:, None] + torch.from_numpy(quad * (np.pi / 2)).to(dev)[None, :]                  # [E, K]
+    c, s = torch.cos(rot)[:, :, None], torch.sin(rot)[:, :, None]
+    x, y = base_t[None, :, :, 0], base_t[None, :, :, 1]
+    paths = torch.stack([c * x - s * y + float(mv), s * x + c * y + float(mv),
+                         torch.remainder(base_t[None, :, :, 2] + rot[:, :, None], 2 * np.pi)], dim=-1).contiguous()
+    lengths = torch.from_numpy(lens).to(dev)[None, :].expand(E, K).contiguous()
+    blank = torch.zeros((S, S), dtype=torch.float64, device=dev)
+    fp = torch.from_numpy(np.ascontiguousarray(np.asarray(footprint, np.float64).reshape(-1, 2))).to(dev)
+    _, sw = env.swath_costs(paths, fp, blank, lengths=lengths, return_swaths=True)
+    first = paths[:, :, :1, :].contiguous()
+    one = torch.clamp(lengths, max=1)
+    for half in ship_halves(footprint):
+        _, cut = env.swath_costs(first, torch.from_numpy(np.ascontiguousarray(half)).to(dev), blank, lengths=one, return_swaths=True)
+        sw = sw & ~cut
+    return (sw.to(torch.int64) << torch.arange(S, dtype=torch.int64, device=dev)).sum(-1)
+
+
+def lattice_full_paths(prims, result, starts):
+    """``AStar.build_path`` for a batch: the sampled path of every env's node path, [E, Pmax, 3] float64 plus lengths [E] int32 (0 for an env without
+    a path), on the device of `result` and ready for ``swath_costs(paths[:, None], ..., lengths=lengths[:, None])``.  Primitive (b, k) that leaves node
+    n is rotated by that node's world heading minus b * spacing and moved to the node; headings are taken mod 2 pi.  Pmax = (max_path_nodes - 1) *
+    (samples of the longest primitive): fixed by the shapes, so nothing is read back."""
+    nodes, edges, n_nodes = result.nodes, result.edges, result.n_nodes
+    dev = nodes.device
+    E, N = edges.shape
+    nb, nem = prims.num_base_h, prims.ne_max
+    Pm = max(prims.samples(b, k).shape[1] for b in range(nb) for k in range(len(prims.edges[b])))
+    tab, cnt = np.zeros((nb * nem, Pm, 3)), np.zeros(nb * nem, np.int64)
+    for b in range(nb):
+        for k in range(len(prims.edges[b])):
+            sm = prims.samples(b, k)
+            tab[b * nem + k, :sm.shape[1]], cnt[b * nem + k] = sm.T, sm.shape[1]
+    tab_t, cnt_t = torch.from_numpy(tab).to(dev), torch.from_numpy(cnt).to(dev)
+    if N < 2:
+        return torch.zeros((E, 0, 3), dtype=torch.float64, device=dev), torch.zeros(E, dtype=torch.int32, device=dev)
+    seg = torch.arange(N - 1, device=dev)[None, :] < (n_nodes.to(torch.int64)[:, None] - 1)      # [E, N-1]: segment n -> n + 1 exists
+    eid = torch.where(seg, edges[:, 1:].to(torch.int64), torch.zeros_like(edges[:, 1:], dtype=torch.int64)).clamp(0, nb * nem - 1)
+    ns = torch.where(seg, cnt_t[eid], torch.zeros_like(eid))                                      # samples per segment
+    off = torch.cumsum(ns, 1) - ns
+    a = nodes[:, :-1, :]
+    theta = a[:, :, 2] - (eid // nem).to(torch.float64) * prims.spacing
+    c, s = torch.cos(theta)[:, :, None], torch.sin(theta)[:, :, None]
+    pp = tab_t[eid]                                                                               # [E, N-1, Pm, 3]
+    x = c * pp[..., 0] - s * pp[..., 1] + a[:, :, None, 0]
+    y = s * pp[..., 0] + c * pp[..., 1] + a[:, :, None, 1]
+    t = torch.remainder(pp[..., 2] + theta[:, :, None], 2 * np.pi)
+    valid = torch.arange(Pm, device=dev)[None, None, :] < ns[:, :, None]
+    Pmax = (N - 1) * Pm
+    dst = torch.where(valid, off[:, :, None] + torch.arange(Pm, device=dev)[None, None, :], torch.full_like(valid, Pmax, dtype=torch.int64))
+    out = torch.zeros((E, Pmax + 1, 3), dtype=torch.float64, device=dev)
+    out.scatter_(1, dst.reshape(E, -1, 1).expand(E, (N - 1) * Pm, 3), torch.stack([x, y, t], -1).reshape(E, -1, 3))
+    return out[:, :Pmax].contiguous(), ns.sum(1).to(torch.int32)

@@ -463,6 +463,47 @@ int32_t bp_sizeof_swath_config(void);
 int bp_swath_cost(bp_handle *h, const bp_swath_config *cfg, const double *cost_maps, const double *paths, const int32_t *lengths, const int32_t *rows,
                   const double *footprint, double *costs, uint8_t *swaths, void *stream);
 
+/* ---- batched lattice A* over the cost maps ----
+ * AStar.search of the reference (baselines/ship_ice_nav/planning_based/utils/a_star_search.py; high-level planner: goal line, no occupancy model, no
+ * smoothing) for every env in one launch, one wavefront per env (DESIGN.md "Lattice search" states the semantics exactly; tests/lattice_ref.py restates
+ * them).  Device memory:
+ *   cost_maps  double [E][H][W] with map_stride doubles between the envs' maps, or one [H][W] map with map_stride 0
+ *   starts     double [E][3] = (x, y, theta) in cells / radians;  goal_y double [E] in cells
+ *   active     uint8 [E] or NULL: envs with 0 are BP_LATTICE_SKIPPED; only their status is written
+ *   masks      uint64 [E or 1][nh * ne_max][S]: word r of key (h * ne_max + k) is row r of the S x S swath mask of edge k taken from a node of
+ *              heading h (bit c = column c), the node at the centre cell; mask_stride words between the envs' tables, 0 for one shared table
+ *   workspace  bp_lattice_workspace_bytes(cfg, E) bytes, 16-byte aligned; contents need not be kept between calls
+ *   status int32 [E]; g double [E] (+inf unless found); expanded int32 [E]; n_nodes int32 [E] (0 unless found);
+ *   nodes double [E][max_path_nodes][3] = (X, Y, world heading) start to goal and edges int32 [E][max_path_nodes] = base * ne_max + k of the edge that led
+ *   to each node, -1 for the start: rows 0 .. n_nodes-1 of found envs are written, nothing else
+ * Host memory (copied into the launch): per base heading b < nb = nh / 4 the edges double [nb][ne_max][2] in lattice units, their headings
+ * int32 [nb][ne_max], their path lengths double [nb][ne_max] in cells and the edge counts int32 [nb].
+ * BP_EINVAL, with nothing launched or written, for: a handle that is not ship-ice, S > 64 or even, nh not 8 / 16 or nb != nh / 4, more than 32 edges per
+ * base heading, an edge that is not a multiple of unit / den or an edge heading outside [0, nh), non-positive sizes or caps, a map whose diagonal exceeds
+ * 4094 sub-units, bad strides, a workspace that is too small or misaligned.  BP_ESTATE before load and reset.  Reads no environment state. */
+enum { BP_LATTICE_FOUND = 0, BP_LATTICE_NO_PATH = 1, BP_LATTICE_CAP = 2, BP_LATTICE_SKIPPED = 3 };
+typedef struct bp_lattice_config {
+    int32_t H, W;               /* rows and columns of a cost map */
+    int32_t S;                  /* mask side = 2 * max_val + 1 <= 64 */
+    int32_t nh, nb;             /* headings (8 or 16), base headings (nh / 4) */
+    int32_t ne_max;             /* second dimension of the edge tables and of the mask keys, <= 32 */
+    int32_t den;                /* sub-units per lattice unit (2 for the reference's 8-heading set: its (1.5, 1.5, 1) edge) */
+    int32_t margin;             /* row window: [max(0, int(y0) - margin), min(H, int(goal_y) + margin)) */
+    int32_t h_baseline;         /* != 0: h = max(0, goal_y - Y) instead of the Dubins heuristic */
+    int32_t max_expansions, node_capacity, queue_capacity, max_path_nodes;   /* caps: exceeding one gives BP_LATTICE_CAP */
+    int32_t pad_;
+    int64_t map_stride, mask_stride;
+    double unit;                /* cells per lattice unit (the primitives' scale) */
+    double weight;              /* f = g + weight * h; 0: f = g */
+    double turning_radius;      /* cells */
+} bp_lattice_config;
+int32_t bp_sizeof_lattice_config(void);
+int64_t bp_lattice_workspace_bytes(const bp_lattice_config *cfg, int32_t num_envs);   /* < 0: BP_EINVAL */
+int bp_lattice_search(bp_handle *h, const bp_lattice_config *cfg, const double *cost_maps, const double *starts, const double *goal_y, const uint8_t *active,
+                      const double *edges_host, const int32_t *edge_headings_host, const double *edge_lengths_host, const int32_t *edge_counts_host,
+                      const uint64_t *masks, void *workspace, int64_t workspace_bytes, int32_t *status, double *g, int32_t *expanded, int32_t *n_nodes,
+                      double *nodes, int32_t *edges, void *stream);
+
 const char *bp_last_error(const bp_handle *h);
 int32_t bp_abi_version(void);
 int32_t bp_sizeof_config(void);   /* sizeof(bp_config), so a binding can verify its struct layout */
