@@ -802,11 +802,8 @@ __global__ __launch_bounds__(256) void k_debug_round2(const double *__restrict__
 
 // ShipIceMetric.reset / update (ship_ice_metric.py:26-69; shared arithmetic in benchpush_amd/metrics/interactive_nav.py) for every env,
 // one thread per env, after the physics kernel of bp_step (mode 0) or the reset kernel of bp_reset (mode 1).
-__global__ __launch_bounds__(256) void k_episode_metrics(const DevParams P, const DevPtrs D, const int mode, const unsigned char *__restrict__ mask)
+__device__ __forceinline__ void episode_metrics_env(const DevParams &P, const DevPtrs &D, const int mode, const unsigned char *__restrict__ mask, const int env)
 {
-    const int env = blockIdx.x * blockDim.x + threadIdx.x;
-    // bp_get_clock_stamps: the shader-clock counters of the XCDs are not synchronised with each other, so the pair is filed under the XCD that took it
-    if (env == 0) { const int x = sq_xcc_id(); D.clk[2 * x] = __builtin_amdgcn_s_memtime(); D.clk[2 * x + 1] = __builtin_amdgcn_s_memrealtime(); }
     if (env >= P.num_envs) return;
     double *a = D.m_acc + (size_t)env * 8;
     const d2 p = D.pxy[(size_t)env * P.nbcap];
@@ -846,6 +843,21 @@ __global__ __launch_bounds__(256) void k_episode_metrics(const DevParams P, cons
     a[6] = D.e_total_work[env];
     a[7] = (double)((fl >> 1) & 1);
     if (fl & 1) { emit(a[7]); D.m_open[env] = 0; }
+}
+__global__ __launch_bounds__(256) void k_episode_metrics(const DevParams P, const DevPtrs D, const int mode, const unsigned char *__restrict__ mask)
+{
+    const int env = blockIdx.x * blockDim.x + threadIdx.x;
+    // bp_get_clock_stamps: the thread of env 0 times its own stay in this kernel with both counters and adds the two differences to running sums.  Counter
+    // values of different launches must not be subtracted from each other: the shader-clock counters that two launches read are not synchronised (their
+    // offsets, ~1e8 cycles, turned a span of 20 ms into clocks between -3 and 8 GHz), whereas both ends of one wave's stay are read in one place.
+    unsigned long long c0 = 0ull, r0 = 0ull;
+    if (env == 0) { c0 = __builtin_amdgcn_s_memtime(); r0 = __builtin_amdgcn_s_memrealtime(); }
+    episode_metrics_env(P, D, mode, mask, env);
+    if (env == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");   // the stay includes the round trips of the env's own loads and stores
+        const unsigned long long c1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
+        D.clk[0] += c1 - c0; D.clk[1] += r1 - r0;
+    }
 }
 
 static int launch(bp_handle *h, int mode, const double *actions, const unsigned char *mask, unsigned char *obs, double *reward,

@@ -47,7 +47,7 @@ struct DevParams {
     int sq_debug;                              // test hook (BP_SCHED_DEBUG_DROP=1): env 1 is parked after its first chunk and never queued, the watchdog is short
     int bias_lanes;                            // 1 (default; BP_BIAS_LANES=0 switches it off): sub-steps with a bias term solve the bias system in mirror lanes of the no-bias passes (substep, 6d)
     int dbg_paths;                             // test hook (BP_DEBUG_PATHS bit mask): 1 no candidate cache, 2 bound rounds through the sequential (flushing) loop,
-                                               // 4 cached planes always through the support query, 8 manifold support vertices always through the support query
+                                               // 4 cached planes always through the support query, 8 manifold support vertices always through the support query, 16 one side per bound round (every pair takes a trip of its own)
     // two environments per wavefront (bp_physics_pair.hpp): 0 off, 1 fixed pairs (2b, 2b + 1) for the whole step (k_physics_step_pair: parity tests),
     // 2 inside the preemptive scheduler (the pair_solo heaviest envs of the dispatch order start alone, the others in pairs)
     int pair_mode, pair_solo;
@@ -122,7 +122,7 @@ struct DevPtrs {
     double *m_sum;           // [E][BP_EPM_COUNT] row fields summed over all finished episodes
     unsigned *m_count;       // [E] finished episodes
     unsigned char *m_open;   // [E] an episode is running (reset seen, not yet terminated)
-    unsigned long long *clk; // [8][2] per XCD: shader-clock counter (s_memtime) and 100 MHz reference (s_memrealtime) stamped after a physics launch by a thread of that XCD  [no record: per device, not per env]
+    unsigned long long *clk; // [8][2], row 0 used: running sums of shader-clock cycles (s_memtime) and 100 MHz reference ticks (s_memrealtime) that the thread of env 0 spent in k_episode_metrics after each physics launch  [no record: per device, not per env]
     // debug  [no record: diagnostics of the handle]
     double *dbg;             // optional [substeps][nbcap][3] pose trace of env dbg_env
     int dbg_env;

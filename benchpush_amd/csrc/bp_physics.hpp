@@ -44,6 +44,11 @@
 #define BP_DBGP(bit) false
 #define BP_TRACE_ON(D) false
 #endif
+// Sides per bound round of the plane search (substep, 4a'): 3 = lane groups of BP_MAXV + 1, 2 = one side per half wave (the mapping before; kept so that the
+// two can be measured against each other: -DBP_BOUND_GROUPS=2).
+#ifndef BP_BOUND_GROUPS
+#define BP_BOUND_GROUPS 3
+#endif
 #include "bp_contact.hpp"   // ArbReg, Manifold, apply_contact_impulses and the lane-local contact arithmetic shared with substep_pair()
 
 struct EnvCtx {
@@ -82,14 +87,14 @@ struct LdsCtx {
     // narrow phase (per candidate round, indexed by survivor rank): best plane separation of side A / B as order-preserving keys, its plane
     // index and support vertex
     unsigned long long *res_smA, *res_smB; // [64]
-    unsigned *res_iA, *res_iB, *res_jA, *res_jB; // [64]
+    unsigned *res_iA, *res_iB, *res_jA, *res_jB; // [64] res_i: plane << 8 | support vertex (one word, so that one atomic minimum settles both); res_j: only part of the aliased AABB keys
     // support queries (support_queries below): direction, (body | vertex count << 16), result value / first index; q_aux / q_c carry the plane
     // a query belongs to (pair rank | side << 8 | plane << 16) and dot(fn, fp) of that plane
     d2 *q_dir;                 // [BP_QCAP]
     double *q_c, *r_val;       // [BP_QCAP]
     unsigned *q_meta, *q_aux, *r_idx; // [BP_QCAP]
     // pair table of a candidate round: what the plane-bound rounds need of each surviving pair
-    uint4 *pt_a;               // [64] sa | sb << 16, nA | nB << 8 | hA << 16 | hB << 24, evaluated sides | jA << 8 | jB << 16, -
+    uint4 *pt_a;               // [64] two side entries (x, y) (z, w): planes' body | searched body << 16, vertex counts n | evaluated << 7 | n_other << 8 | cached plane << 16 | its support vertex << 24
     d2 *pt_thr;                // [64] separation of the cached plane of side A / B (-inf: none)
     // candidate cache: what the lanes of the FIRST candidate round found out about their (moving body, neighbour slot) -- body indices, slot, vertex
     // counts, the static part of the pair filter -- and the slot's hint word, valid while the moving list and the neighbour lists stay as they are
@@ -509,88 +514,95 @@ __device__ __forceinline__ void substep(const DevParams &P, const EnvCtx &E, con
         PROF_CNT(18, __popcll(cm))
         if (cm == 0) continue;
         PROF_CNT(25, 1)
-        // ---- 4a'. every other plane of the surviving pairs: one round per pair, lanes 0..31 = planes of A, 32..63 = planes of B.  A plane's separation
+        // ---- 4a'. every other plane of the surviving pairs: one side of a pair per lane group and round (the mapping is stated at the fast path below).  A plane's separation
         //      is a minimum over the other shape's vertices, so its minimum over THREE of them (the support vertex of the side's cached plane and its two
         //      neighbours) bounds it from above; only planes whose bound reaches the cached plane's exact value can win the side (ties included) and are searched exactly.
         const int nc = __popcll(cm);
         const int myr = popc_below(cm, lane); // rank of this lane's pair among the survivors
         const int nA_l = valid ? nA_h : 0, nB_l = valid ? nB_h : 0;
         if (valid) {
-            uint4 pa;
+            uint4 pa;   // (x, y) = the entry of side A, (z, w) = that of side B
             pa.x = (unsigned)sa | ((unsigned)sb << 16);
-            pa.y = (unsigned)nA_l | ((unsigned)nB_l << 8) | ((unsigned)hA << 16) | ((unsigned)hB << 24);
-            pa.z = (evA ? 1u : 0u) | (evB ? 2u : 0u) | ((unsigned)jAc << 8) | ((unsigned)jBc << 16);
-            pa.w = 0u;
+            pa.y = (unsigned)nA_l | (evA ? 0x80u : 0u) | ((unsigned)nB_l << 8) | ((unsigned)hA << 16) | ((unsigned)jAc << 24);
+            pa.z = (unsigned)sb | ((unsigned)sa << 16);
+            pa.w = (unsigned)nB_l | (evB ? 0x80u : 0u) | ((unsigned)nA_l << 8) | ((unsigned)hB << 16) | ((unsigned)jBc << 24);
             L.pt_a[myr] = pa;
             L.pt_thr[myr] = mk2(sepAc, sepBc);
-            L.res_smA[myr] = evA ? f64_key(sepAc) : 0ull; L.res_iA[myr] = evA ? (unsigned)hA : 0xFFFFFFFFu; L.res_jA[myr] = (unsigned)jAc;
-            L.res_smB[myr] = evB ? f64_key(sepBc) : 0ull; L.res_iB[myr] = evB ? (unsigned)hB : 0xFFFFFFFFu; L.res_jB[myr] = (unsigned)jBc;
+            L.res_smA[myr] = evA ? f64_key(sepAc) : 0ull; L.res_iA[myr] = evA ? ((unsigned)hA << 8) | (unsigned)jAc : 0xFFFFFFFFu;
+            L.res_smB[myr] = evB ? f64_key(sepBc) : 0ull; L.res_iB[myr] = evB ? ((unsigned)hB << 8) | (unsigned)jBc : 0xFFFFFFFFu;
         }
         lds_sync();
         {
             int nq = 0, g0 = 0; // queries collected, first pair rank of the current group
-            const int side = lane >> 5, f = lane & 31;
-            // One bound round: lanes 0..31 = planes of A, 32..63 = planes of B of the pair with rank rr.
-            auto round_addr = [&](const uint4 pa, int &pbody, int &qbody, int &np, int &nqv, int &hX, bool &evX, int &jc, int &jm, int &jp) {
-                const int psa = (int)(pa.x & 0xFFFFu), psb = (int)(pa.x >> 16);
-                const int pna = (int)(pa.y & 0xFFu), pnb = (int)((pa.y >> 8) & 0xFFu);
-                pbody = side ? psb : psa; qbody = side ? psa : psb;
-                np = side ? pnb : pna; nqv = side ? pna : pnb;
-                hX = (int)((pa.y >> (side ? 24 : 16)) & 0xFFu);
-                evX = ((pa.z >> side) & 1u) != 0;
-                jc = (int)((pa.z >> (side ? 16 : 8)) & 0xFFu);
+            // The pair table read side by side: entry t = 2 * rank + side names the body that owns the planes, the body whose vertices are searched, their
+            // vertex counts, the side's cached plane and that plane's support vertex (here with its cyclic neighbours); pts_thr[t] is the cached plane's separation.
+            const uint2 *const pts = (const uint2 *)L.pt_a;
+            const double *const pts_thr = (const double *)L.pt_thr;
+            auto round_addr = [&](const uint2 e, int &pbody, int &qbody, int &np, int &nqv, int &hX, bool &evX, int &jc, int &jm, int &jp) {
+                pbody = (int)(e.x & 0xFFFFu); qbody = (int)(e.x >> 16);
+                np = (int)(e.y & 0x7Fu); evX = (e.y & 0x80u) != 0; nqv = (int)((e.y >> 8) & 0xFFu);
+                hX = (int)((e.y >> 16) & 0xFFu); jc = (int)(e.y >> 24);
                 jm = (jc == 0) ? max(nqv, 1) - 1 : jc - 1; jp = (jc + 1 >= nqv) ? 0 : jc + 1;   // cyclic neighbours of the support vertex
             };
-            // Fast path: the rounds are taken two at a time so that their loads travel together; the surviving planes go straight into the query
-            // buffer.  If they do not all fit (rare: pairs without cached planes), the sequential loop below redoes the rounds group by group.
+            // Fast path: a round serves IPR sides, each in a group of GW lanes (lane l: group g = l / GW, plane f = l - GW g; a hull has at most BP_MAXV = 20
+            // planes, so 21 lanes hold a side and lane 63 idles).  The sides of the surviving pairs are numbered t = 2 * rank + side; the rounds are taken
+            // two at a time so that their loads travel together, i.e. a trip serves the 2 IPR sides of IPR pairs.  The surviving planes go straight into
+            // the query buffer: their order there does not matter, since the per-side maxima are resolved by atomics on keys.  If they do not all fit
+            // (rare: pairs without cached planes), the sequential loop below redoes the rounds group by group.
             int rr_start = nc;
             {
+                constexpr int GW = (BP_BOUND_GROUPS == 3 && KIND != BP_ENV_BOX) ? BP_MAXV + 1 : 32, IPR = 64 / GW;
+                static_assert(GW >= BP_MAXV && IPR * GW <= 64, "a lane group holds every plane of a side");
+                const int g = lane / GW, f = lane - g * GW;
+                const int ipr = BP_DBGP(16) ? 1 : IPR;                   // sides per round == pairs per trip
                 bool fits = !BP_DBGP(2);
-                for (int r0 = 0; r0 < nc && fits; r0 += 2) {
-                    const bool two = r0 + 1 < nc;
-                    const uint4 pa0 = L.pt_a[r0], pa1 = L.pt_a[two ? r0 + 1 : r0];
-                    const d2 thr0 = L.pt_thr[r0], thr1 = L.pt_thr[two ? r0 + 1 : r0];
+                for (int r0 = 0; r0 < nc && fits; r0 += ipr) {
+                    // the lane's side in the first round of the trip is 2 r0 + g, in the second ipr sides further on
+                    const bool on0 = g < ipr && 2 * r0 + g < 2 * nc, on1 = g < ipr && 2 * r0 + ipr + g < 2 * nc;
+                    const int ta = on0 ? 2 * r0 + g : 2 * r0, tb = on1 ? 2 * r0 + ipr + g : 2 * r0;
+                    const uint2 e0 = pts[ta], e1 = pts[tb];
+                    const double th0 = pts_thr[ta], th1 = pts_thr[tb];
                     int pb0, qb0, np0, nqv0, hX0, jc0, jm0, jp0, pb1, qb1, np1, nqv1, hX1, jc1, jm1, jp1; bool ev0, ev1;
-                    round_addr(pa0, pb0, qb0, np0, nqv0, hX0, ev0, jc0, jm0, jp0);
-                    round_addr(pa1, pb1, qb1, np1, nqv1, hX1, ev1, jc1, jm1, jp1);
+                    round_addr(e0, pb0, qb0, np0, nqv0, hX0, ev0, jc0, jm0, jp0);
+                    round_addr(e1, pb1, qb1, np1, nqv1, hX1, ev1, jc1, jm1, jp1);
                     const int fc0 = (f < np0) ? f : 0, fc1 = (f < np1) ? f : 0;
                     const d2 fn0 = gE(E.wn, pb0 * BP_MAXV + fc0), fp0 = gE(E.wv, pb0 * BP_MAXV + fc0), vb0 = gE(E.wv, qb0 * BP_MAXV + jc0), vm0 = gE(E.wv, qb0 * BP_MAXV + jm0), vp0 = gE(E.wv, qb0 * BP_MAXV + jp0);
                     const d2 fn1 = gE(E.wn, pb1 * BP_MAXV + fc1), fp1 = gE(E.wv, pb1 * BP_MAXV + fc1), vb1 = gE(E.wv, qb1 * BP_MAXV + jc1), vm1 = gE(E.wv, qb1 * BP_MAXV + jm1), vp1 = gE(E.wv, qb1 * BP_MAXV + jp1);
                     {
-                        const double th = side ? thr0.y : thr0.x;
-                        const bool pv = (f < np0) && !(ev0 && f == hX0);
+                        const bool pv = on0 && (f < np0) && !(ev0 && f == hX0);
                         const double c = vdot(fn0, fp0);
                         const double bound = (fmin(vdot(fn0, vb0), fmin(vdot(fn0, vm0), vdot(fn0, vp0))) - c) + 0.0;
-                        const bool surv = pv && (!ev0 || bound >= th);
+                        const bool surv = pv && (!ev0 || bound >= th0);
                         const unsigned long long sm = ballot(surv);
                         const int sl = nq + popc_below(sm, lane);
                         if (surv && sl < BP_QCAP) {
                             L.q_dir[sl] = fn0; L.q_meta[sl] = (unsigned)qb0 | ((unsigned)nqv0 << 16);
-                            L.q_aux[sl] = (unsigned)r0 | ((unsigned)side << 8) | ((unsigned)f << 16);
+                            L.q_aux[sl] = (unsigned)(ta >> 1) | ((unsigned)(ta & 1) << 8) | ((unsigned)f << 16);
                             L.q_c[sl] = c;
                         }
                         nq += __popcll(sm);
                     }
                     {
-                        const double th = side ? thr1.y : thr1.x;
-                        const bool pv = two && (f < np1) && !(ev1 && f == hX1);
+                        const bool pv = on1 && (f < np1) && !(ev1 && f == hX1);
                         const double c = vdot(fn1, fp1);
                         const double bound = (fmin(vdot(fn1, vb1), fmin(vdot(fn1, vm1), vdot(fn1, vp1))) - c) + 0.0;
-                        const bool surv = pv && (!ev1 || bound >= th);
+                        const bool surv = pv && (!ev1 || bound >= th1);
                         const unsigned long long sm = ballot(surv);
                         const int sl = nq + popc_below(sm, lane);
                         if (surv && sl < BP_QCAP) {
                             L.q_dir[sl] = fn1; L.q_meta[sl] = (unsigned)qb1 | ((unsigned)nqv1 << 16);
-                            L.q_aux[sl] = (unsigned)(r0 + 1) | ((unsigned)side << 8) | ((unsigned)f << 16);
+                            L.q_aux[sl] = (unsigned)(tb >> 1) | ((unsigned)(tb & 1) << 8) | ((unsigned)f << 16);
                             L.q_c[sl] = c;
                         }
                         nq += __popcll(sm);
                     }
+                    PROF_CNT(49, 1)
                     fits = nq <= BP_QCAP;
                 }
                 if (!fits) { nq = 0; rr_start = 0; }
                 lds_sync();
             }
+            const int side = lane >> 5, f = lane & 31; // the flushing loop: one pair per round, lanes 0..31 = planes of A, 32..63 = planes of B
             for (int rr = rr_start; rr <= nc; rr++) {
                 // the queries collected so far are searched when the next round might not fit, and after the last pair
                 if (nq > 0 && (rr == nc || nq + 64 > BP_QCAP)) {
@@ -617,26 +629,14 @@ __device__ __forceinline__ void substep(const DevParams &P, const EnvCtx &E, con
                         if (evB && f64_key(sepBc) != L.res_smB[myr]) L.res_iB[myr] = 0xFFFFFFFFu;
                     }
                     lds_sync();
+                    // a plane's index travels with its support vertex (plane << 8 | vertex): the lowest plane among a side's maxima brings its own vertex along
                     for (int s0 = 0; s0 < nq; s0 += 64) {
                         const int sl = s0 + lane;
                         if (sl < nq) {
                             const unsigned aux = L.q_aux[sl];
                             const int r = (int)(aux & 0xFFu);
                             const unsigned long long key = __builtin_bit_cast(unsigned long long, L.q_c[sl]);
-                            if (key == ((aux & 0x100u) ? L.res_smB[r] : L.res_smA[r])) atomicMin((aux & 0x100u) ? &L.res_iB[r] : &L.res_iA[r], aux >> 16);
-                        }
-                    }
-                    lds_sync();
-                    for (int s0 = 0; s0 < nq; s0 += 64) {
-                        const int sl = s0 + lane;
-                        if (sl < nq) {
-                            const unsigned aux = L.q_aux[sl];
-                            const int r = (int)(aux & 0xFFu);
-                            const unsigned long long key = __builtin_bit_cast(unsigned long long, L.q_c[sl]);
-                            const bool onB = (aux & 0x100u) != 0;
-                            if (key == (onB ? L.res_smB[r] : L.res_smA[r]) && (aux >> 16) == (onB ? L.res_iB[r] : L.res_iA[r])) {
-                                if (onB) L.res_jB[r] = L.r_idx[sl]; else L.res_jA[r] = L.r_idx[sl];
-                            }
+                            if (key == ((aux & 0x100u) ? L.res_smB[r] : L.res_smA[r])) atomicMin((aux & 0x100u) ? &L.res_iB[r] : &L.res_iA[r], ((aux >> 16) << 8) | L.r_idx[sl]);
                         }
                     }
                     lds_sync();
@@ -644,11 +644,10 @@ __device__ __forceinline__ void substep(const DevParams &P, const EnvCtx &E, con
                     PROF_ACC(30)
                 }
                 if (rr == nc) break;
-                const uint4 pa = L.pt_a[rr];
-                const d2 thr = L.pt_thr[rr];
+                const uint2 e = pts[2 * rr + side];
+                const double th = pts_thr[2 * rr + side];
                 int pbody, qbody, np, nqv, hX, jc, jm, jp; bool evX;
-                round_addr(pa, pbody, qbody, np, nqv, hX, evX, jc, jm, jp);
-                const double th = side ? thr.y : thr.x;
+                round_addr(e, pbody, qbody, np, nqv, hX, evX, jc, jm, jp);
                 const bool pv = (f < np) && !(evX && f == hX);
                 const int fc = (f < np) ? f : 0;
                 const d2 fn = gE(E.wn, pbody * BP_MAXV + fc), fp = gE(E.wv, pbody * BP_MAXV + fc);
@@ -683,7 +682,8 @@ __device__ __forceinline__ void substep(const DevParams &P, const EnvCtx &E, con
         const int oA = sa * BP_MAXV, oB = sb * BP_MAXV;
         if (valid) {
             const double sA = key_f64(L.res_smA[myr]), sB = key_f64(L.res_smB[myr]);
-            iA = (int)L.res_iA[myr]; iB = (int)L.res_iB[myr]; jA = (int)L.res_jA[myr]; jB = (int)L.res_jB[myr];
+            const unsigned wA = L.res_iA[myr], wB = L.res_iB[myr];   // winning plane << 8 | its support vertex
+            iA = (int)(wA >> 8); iB = (int)(wB >> 8); jA = (int)(wA & 0xFFu); jB = (int)(wB & 0xFFu);
             const bool useA = (sA >= sB);
             const double smax = useA ? sA : sB;
             touching = true;

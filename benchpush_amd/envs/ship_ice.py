@@ -512,18 +512,18 @@ class BatchedShipIceEnv(_BatchedBase):
         return out.astype(np.uint64) << 8
 
     def clock_stamps(self):
-        """uint64 [8, 2]: per XCD the latest (shader-clock counter, 100 MHz reference counter) pair stamped after a physics launch by a thread of that
-        XCD (zeros: none yet).  `clock_hz_between` turns two readings into the clock the chip held in between."""
+        """uint64 [8, 2], row 0 used (the others stay zero): running sums of (shader-clock cycles, 100 MHz reference ticks) that one thread spent in the
+        small kernel that follows every physics launch, each stay timed by that thread with both counters.  `clock_hz_between` turns two readings into the
+        clock the chip held during the stays in between."""
         out = np.zeros((8, 2), np.uint64)
         _lib.check(self.L, self.h, self.L.bp_get_clock_stamps(self.h, out.ctypes.data_as(C.c_void_p)), "bp_get_clock_stamps")
         return out
 
     @staticmethod
     def clock_hz_between(c0, c1, with_span=False):
-        """Shader clock between two `clock_stamps()` readings: both counters of ONE XCD (the counters of different XCDs are not synchronised).  Only the
-        thread of env 0 stamps, so most XCDs are refreshed rarely: an XCD whose first stamp is old (load, warm-up) would bring idle clocks into the span.  The
-        XCD chosen is therefore the one whose FIRST stamp is the newest -- closest to the start of the timed region -- among those stamped again afterwards.
-        Returns (hz, xcd) or (None, None) if no XCD was stamped before both readings; with_span=True appends the reference-time span in seconds."""
+        """Shader clock between two `clock_stamps()` readings: cycles over reference time of the stays summed in between (sampled right after each physics
+        launch; a stay is a few microseconds, so a handful of launches resolve the clock to about a percent).  The rows are scanned as before; only row 0
+        is filled.  Returns (hz, row) or (None, None) if nothing was summed before both readings; with_span=True appends the summed reference time in seconds."""
         best = None
         for x in range(8):
             if c0[x, 1] == 0 or c1[x, 1] <= c0[x, 1]:
@@ -538,7 +538,7 @@ class BatchedShipIceEnv(_BatchedBase):
 
     @staticmethod
     def clock_per_xcd(c0, c1):
-        """Every XCD that was stamped before both readings: [{xcd, mhz, span_ms}] -- what `clock_hz_between` chose from (a short span reads noisier)."""
+        """Every row that was summed before both readings: [{xcd, mhz, span_ms}] -- what `clock_hz_between` chose from (a short span reads noisier)."""
         out = []
         for x in range(8):
             if c0[x, 1] == 0 or c1[x, 1] <= c0[x, 1]:

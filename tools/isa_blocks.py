@@ -10,11 +10,11 @@ import re
 import sys
 
 # phases of substep() as line ranges of csrc/bp_physics.hpp (update when the file moves; `grep -n "// ---- " csrc/bp_physics.hpp`)
-PH = [(272, 288, '0head'), (289, 362, '1integrate'), (363, 376, '2refresh'), (377, 461, '3candidates'), (462, 511, '4a_cached_planes'),
-      (512, 670, '4a_bound_rounds+search'), (671, 840, '4b_manifold'), (841, 944, '4c_deliver'), (945, 957, '5events+filter'),
+PH = [(277, 293, '0head'), (294, 367, '1integrate'), (368, 381, '2refresh'), (382, 466, '3candidates'), (467, 516, '4a_cached_planes'),
+      (517, 669, '4a_bound_rounds+search'), (670, 840, '4b_manifold'), (841, 944, '4c_deliver'), (945, 957, '5events+filter'),
       (958, 974, '6a_prestep'), (975, 1002, '6a_warmset'), (1003, 1042, '6a_colour'), (1043, 1068, '6b_velint'), (1069, 1092, '6c_warmstart'),
-      (1093, 1280, '6d_solver'), (1281, 1335, '7post'), (1336, 1402, '7mvlist'), (237, 261, 'support_queries'), (207, 229, 'world_from_pose'),
-      (154, 204, 'refresh_body')]
+      (1093, 1280, '6d_solver'), (1281, 1335, '7post'), (1336, 1402, '7mvlist'), (242, 266, 'support_queries'), (212, 234, 'world_from_pose'),
+      (159, 209, 'refresh_body')]
 
 
 def phase_of(chain):
