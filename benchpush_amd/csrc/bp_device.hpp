@@ -47,7 +47,8 @@ struct DevParams {
     int sq_debug;                              // test hook (BP_SCHED_DEBUG_DROP=1): env 1 is parked after its first chunk and never queued, the watchdog is short
     int bias_lanes;                            // 1 (default; BP_BIAS_LANES=0 switches it off): sub-steps with a bias term solve the bias system in mirror lanes of the no-bias passes (substep, 6d)
     int dbg_paths;                             // test hook (BP_DEBUG_PATHS bit mask): 1 no candidate cache, 2 bound rounds through the sequential (flushing) loop,
-                                               // 4 cached planes always through the support query, 8 manifold support vertices always through the support query, 16 one side per bound round (every pair takes a trip of its own)
+                                               // 4 cached planes always through the support query, 8 manifold support vertices always through the support query, 16 one side per bound round (every pair takes a trip of its own),
+                                               // 32 manifold phase with one lane per pair (the text box-delivery keeps) instead of one per side, 64 one pair per trip of the manifold phase
     // two environments per wavefront (bp_physics_pair.hpp): 0 off, 1 fixed pairs (2b, 2b + 1) for the whole step (k_physics_step_pair: parity tests),
     // 2 inside the preemptive scheduler (the pair_solo heaviest envs of the dispatch order start alone, the others in pairs)
     int pair_mode, pair_solo;
@@ -206,9 +207,9 @@ __host__ __device__ inline LdsMap bp_lds_map(const int nbcap, const int mvcap, c
     m.cc = p; p += 8u * 64;                   // candidate cache of the first candidate round (persists across sub-steps)
     m.cc_hw = p; p += 8u * 64;
     m.res_smA = p; p += 8u * 64;              // res_smA .. res_jB are contiguous: the AABB keys of the transform phase ([64][4] u64) alias them
-    m.res_smB = p; p += 8u * 64;
+    m.res_smB = m.res_smA + 8u * 64; p += 8u * 64;   // side B of res_sm / res_i lies 64 entries after side A by construction: manifold_lanes (bp_physics.hpp) indexes them as [side][64]
     m.res_iA = p; p += 4u * 64;
-    m.res_iB = p; p += 4u * 64;
+    m.res_iB = m.res_iA + 4u * 64; p += 4u * 64;
     m.res_jA = p; p += 4u * 64;
     m.res_jB = p; p += 4u * 64;
     m.mvs = p; p += 4u * (unsigned)nbcap;

@@ -21,11 +21,15 @@
 #define PROF_ACC(slot) { unsigned long long _n = __builtin_amdgcn_s_memtime(); if (lane_id() == 0) L.prof[slot] += _n - _pt; _pt = _n; }
 #define PROF_CNT(slot, v) { const unsigned long long _v = (unsigned long long)(v); if (lane_id() == 0) L.prof[slot] += _v; }
 #define PROF_MAX(slot, v) { const unsigned long long _v = (unsigned long long)(v); if (lane_id() == 0 && _v > L.prof[slot]) L.prof[slot] = _v; }
+#define PROF_PARAM , unsigned long long &_pt   // a phase of substep() that lives in a function of its own carries the running stamp along
+#define PROF_ARG , _pt
 #else
 #define PROF_DECL
 #define PROF_ACC(slot)
 #define PROF_CNT(slot, v)
 #define PROF_MAX(slot, v)
+#define PROF_PARAM
+#define PROF_ARG
 #endif
 
 
@@ -48,6 +52,11 @@
 // two can be measured against each other: -DBP_BOUND_GROUPS=2).
 #ifndef BP_BOUND_GROUPS
 #define BP_BOUND_GROUPS 3
+#endif
+// Lanes per surviving pair in the manifold phase (substep, 4b / 4c): 2 = one lane per side of a pair (manifold_lanes below), 1 = one lane per pair (the mapping before and
+// the one box-delivery keeps; -DBP_MANIFOLD_LANES=1 restores it everywhere so that the two can be measured against each other).
+#ifndef BP_MANIFOLD_LANES
+#define BP_MANIFOLD_LANES 2
 #endif
 #include "bp_contact.hpp"   // ArbReg, Manifold, apply_contact_impulses and the lane-local contact arithmetic shared with substep_pair()
 
@@ -265,6 +274,224 @@ __device__ __forceinline__ void support_queries(const EnvCtx &E, const LdsCtx &L
     }
 }
 
+// 4c, the arbiter side of a hand-over batch: dm = the lanes that delivered a manifold, in mailbox order from entry -dbase on; keyv = their pair keys (shapeA << 16 | shapeB).
+__device__ __forceinline__ void arbiters_take(const EnvCtx &E, const LdsCtx &L, ArbReg &A, SubState &S, const unsigned long long dm, const int dbase,
+                                              const unsigned keyv, const unsigned now)
+{
+    const int lane = lane_id();
+    int my_mb = -1;
+    bool fresh = false;
+    unsigned long long m = dm;
+    int dr = 0;
+    while (m) { // every arbiter lane looks for its pair among the delivered ones; a pair nobody owns gets a free slot (rare)
+        const int l = __ffsll((long long)m) - 1;
+        m &= m - 1;
+        if (dr >= dbase && dr < dbase + BP_MBOX) {
+            const unsigned key = (unsigned)__builtin_amdgcn_readlane((int)keyv, l);
+            const bool own = (A.key == key);
+            if (BP_UNLIKELY2(!ballot(own))) {
+                const unsigned long long om = ballot(A.key == ARB_FREE_KEY);
+                if (!om) S.err |= BP_ERR_ARB_OVERFLOW;
+                else {
+                    const int owner = __ffsll((long long)om) - 1;
+                    const int s1 = slot_get(L, S, E.pxy, (int)(key >> 16)), s2 = slot_get(L, S, E.pxy, (int)(key & 0xFFFFu));
+                    if (lane == owner) { my_mb = dr - dbase; fresh = true; A.key = key; A.slotA = s1; A.slotB = s2; }
+                }
+            } else if (own) my_mb = dr - dbase;
+        }
+        dr++;
+    }
+    if (my_mb >= 0) {
+        const d2 *mb = L.mbox + my_mb * 6;
+        const d2 mn_ = mb[0], mp10 = mb[1], mp20 = mb[2], mp11 = mb[3], mp21 = mb[4], mh = mb[5];
+        const d2 pa = L.sp[A.slotA], pbp = L.sp[A.slotB];
+        const unsigned mh0 = (unsigned)__double2hiint(mh.x), mh1 = (unsigned)__double2hiint(mh.y);
+        const int mcount = __double2loint(mh.x);
+        if (BP_UNLIKELY2(fresh)) { // masses and material products of a pair stay with its arbiter
+            const int usa = (int)(A.key >> 16), usb = (int)(A.key & 0xFFFFu);
+            arbiter_adopt(A, gE(E.mass, usa), gE(E.mass, usb), gE(E.prop, usa), gE(E.prop, usb));
+        }
+        arbiter_update(A, mn_, mp10, mp20, mp11, mp21, mh0, mh1, mcount, pa, pbp, now);
+    }
+}
+
+// value that the other lane of a lane pair (2r, 2r + 1) holds: DPP quad_perm [1,0,3,2].  Called in wave-uniform control flow only (an inactive lane is not read).
+__device__ __forceinline__ int mate_i32(const int v) { return __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xF, 0xF, false); }
+__device__ __forceinline__ double mate_f64(const double v) { return dpp_mov_f64<0xB1>(v); }
+__device__ __forceinline__ d2 mate_d2(const d2 v) { return mk2(mate_f64(v.x), mate_f64(v.y)); }
+
+// ---- 4b / 4c with one lane per SIDE of a surviving pair (BP_MANIFOLD_LANES == 2; every instantiation but box-delivery's) ----------------------------------
+// Closest features -> normal -> Chipmunk ContactPoints -> hand-over to the arbiter lanes, for the nc survivors of a candidate round whose plane search has been
+// resolved into the rank tables (pt_a, res_sm*, res_i*; res_jA: the candidate lane's word).  Lanes 2r and 2r + 1 take survivor r0 + r as shape A and shape B, a
+// trip serves 32 survivors.  With one lane per pair nearly every line of the phase is written twice, once per shape, and a mean round has 3 live lanes of 64; here
+// a lane loads the own shape's winning plane, edge and outer neighbours and the other shape's support vertex, tests the own span and tie, certifies the own
+// support vertex, selects the own contact edge and interpolates the own shape's two contact points.  What the two sides owe each other crosses with DPP: the
+// separation and the winner word, (span, s > 0) and the tie bit, the normal from the lane that owns it, two edge cross products, one contact point, one vertex
+// index and one hit bit.  Every floating-point value comes from the operands and the operation order of the one-lane text (substep, 4b); only the lane that
+// evaluates it differs.  "O" = the lane's own shape, "Q" = the other one; "primary" = the side with the larger separation (A on a tie: useA of the one-lane text).
+// Lanes without a survivor run on survivor r0's tables (valid addresses) and are masked by `on`; the DPP exchanges stand outside every divergent branch.
+// P is read by BP_DBGP alone: in the product build it is unused and a trip always serves 32 pairs.
+template <int VL>
+__device__ __forceinline__ void manifold_lanes(const DevParams &P, const EnvCtx &E, const LdsCtx &L, ArbReg &A, SubState &S, const int nc, const bool first_round,
+                                               const unsigned now PROF_PARAM)
+{
+    const int lane = lane_id();
+    const int sd = lane & 1;                                 // 0: this lane is shape A of its pair, 1: shape B
+    const int ppt = BP_DBGP(64) ? 1 : 32;                    // pairs per trip
+    const uint2 *const pts = (const uint2 *)L.pt_a;          // [rank][side] (round_addr of 4a')
+    const unsigned long long *const res_sm = L.res_smA;      // [side][64]: bp_lds_map places res_smB (res_iB) 64 entries after res_smA (res_iA)
+    const unsigned *const res_i = L.res_iA;
+    for (int r0 = 0; r0 < nc; r0 += ppt) {
+        PROF_CNT(50, 1)   // manifold trips
+        const bool on = (lane >> 1) < ppt && r0 + (lane >> 1) < nc;
+        const int r = on ? r0 + (lane >> 1) : r0;
+        const uint2 e = pts[2 * r + sd];
+        const unsigned w = res_i[sd * 64 + r];               // winning plane << 8 | its support vertex on the other shape
+        const double sO = key_f64(res_sm[sd * 64 + r]);
+        const unsigned cw = L.res_jA[r];                     // candidate lane's i | slot << 14 | flagonly << 19 | lane << 20
+        const int oO = (int)(e.x & 0xFFFFu) * BP_MAXV, oQ = (int)(e.x >> 16) * BP_MAXV;
+        const int nO = (int)(e.y & 0x7Fu), nQ = (int)((e.y >> 8) & 0xFFu);
+        const int iO = (int)(w >> 8), jO = (int)(w & 0xFFu);
+        // every vertex / normal the cases below can need of the own side is fetched up front: the winning edge (a, b), its plane normal, the support vertex on the
+        // other shape and the outer neighbours of the edge, which certify the support vertex of the shape that owns the normal
+        const int iO0 = (iO == 0) ? nO - 1 : iO - 1;
+        const int iO0m = (iO0 == 0) ? nO - 1 : iO0 - 1, iOp = (iO + 1 >= nO) ? 0 : iO + 1;
+        const d2 nOi = gE(E.wn, oO + iO);
+        const d2 aO = gE(E.wv, oO + iO0), bO = gE(E.wv, oO + iO), qO = gE(E.wv, oQ + jO);
+        const d2 oO0 = gE(E.wv, oO + iO0m), oO1 = gE(E.wv, oO + iOp);
+        const double rO = gE(E.prop, (int)(e.x & 0xFFFFu)).x, rQ = gE(E.prop, (int)(e.x >> 16)).x;
+        const double rsum = sd ? rQ + rO : rO + rQ;          // radA + radB
+        const double sQ = mate_f64(sO);
+        const unsigned wQ = (unsigned)mate_i32((int)w);
+        const int iQ = (int)(wQ >> 8), jQ = (int)(wQ & 0xFFu);
+        const bool prim = sd ? !(sQ >= sO) : (sO >= sQ);     // useA on the lane of A, !useA on the lane of B
+        const double smax = prim ? sO : sQ;
+        const bool far = smax > rsum, deep = smax <= 0.0;
+        const d2 eO = vsub(bO, aO);
+        const double uO = vdot(vsub(qO, aO), eO), eeO = vdot(eO, eO);
+        const bool spanO = !(uO < 0.0) && !(uO > eeO), posO = sO > 0.0;
+        const int xb = mate_i32((spanO ? 1 : 0) | (posO ? 2 : 0));
+        const bool spanQ = (xb & 1) != 0, posQ = (xb & 2) != 0;
+        // The cascade of the one-lane text in terms of the primary side P and the secondary side S: the plane of P if its support vertex lies over the edge, else
+        // that of S if S separates and spans, else P by its tie partner, else S by its, else the vertex pair of P.
+        const bool spanP = prim ? spanO : spanQ, spanS = prim ? spanQ : spanO, posS = prim ? posQ : posO;
+        const bool open = on && !far && !deep && !spanP && !(posS && spanS);   // the tie tests decide (rare: the neighbour is fetched only here)
+        bool tieO = false;
+        if (open && (prim || posO)) {
+            // facing edges that are parallel to rounding and overlap only partly (tie_partner of the one-lane text, with its comment)
+            const int jn = (uO < 0.0) ? ((jO == 0) ? nQ - 1 : jO - 1) : ((jO + 1 >= nQ) ? 0 : jO + 1);
+            const d2 q1 = gE(E.wv, oQ + jn);
+            const double u1 = vdot(vsub(q1, aO), eO);
+            tieO = !(u1 < 0.0) && !(u1 > eeO) && (vdot(nOi, q1) - vdot(nOi, qO) <= BP_TIE_TOL);
+        }
+        const bool tieQ = mate_i32(tieO ? 1 : 0) != 0;
+        const bool tieP = prim ? tieO : tieQ, tieS = prim ? tieQ : tieO;
+        const bool byP = deep || spanP || (!(posS && spanS) && tieP);
+        const bool byS = !byP && posS && (spanS || tieS);
+        const bool mine = prim ? byP : byS;                  // the normal is the own winning plane's (negated on the lane of B)
+        const bool vpair = !byP && !byS;                     // ... or that of a vertex pair, evaluated by the primary side
+        d2 nM = sd ? vneg(nOi) : nOi;
+        bool tO = true;
+        if (on && !far && vpair && prim) {
+            const d2 c = (uO < 0.0) ? aO : bO;
+            const d2 pp = sd ? vsub(c, qO) : vsub(qO, c);
+            const double dl = vlen(pp);
+            if (dl > rsum) tO = false;
+            nM = vmul(pp, 1.0 / (dl + BP_DBL_MIN));
+        }
+        const d2 nX = mate_d2(nM);
+        const bool tQ = mate_i32(tO ? 1 : 0) != 0;
+        const d2 n = (mine || (vpair && prim)) ? nM : nX;
+        const bool touching = on && !far && tO && tQ;
+        const d2 nO_ = sd ? vneg(n) : n;                     // the normal as the own shape sees it: n on A, -n on B
+        // counters of this phase (slots 50..55; 56 and up are k_observe's): two counts share a slot where it says so, the second in the high word
+        PROF_CNT(51, (unsigned long long)__popcll(ballot(touching && sd == 0 && !vpair && mine)) | ((unsigned long long)__popcll(ballot(touching && sd == 1 && !vpair && mine)) << 32))   // normals: plane of A | plane of B
+        PROF_CNT(52, __popcll(ballot(touching && sd == 0 && vpair)))                                                                                                                      // normals: vertex pair
+        // Support vertices (PolySupportPointIndex; the argument stands at the one-lane text).  The shape that does not own the normal: the support vertex the plane
+        // search found for the other side's winning plane.  The shape that owns it: one end of the winning edge if both outer neighbours stay BP_SUPPORT_MARGIN
+        // below; otherwise, and for vertex-pair normals, a support query.
+        int i1 = jQ;
+        bool need = touching && (mine || vpair);
+        if (touching && mine) {
+            const double c0 = vdot(aO, nO_), c1 = vdot(bO, nO_), o0 = vdot(oO0, nO_), o1 = vdot(oO1, nO_);
+            const double cm = (c0 > c1) ? c0 : c1, om = (o0 > o1) ? o0 : o1;
+            if ((nO == 2 || cm >= om + BP_SUPPORT_MARGIN) && !BP_DBGP(8)) { i1 = (c0 > c1) ? iO0 : (c1 > c0) ? iO : min(iO0, iO); need = false; }
+        }
+        if (on && sd == 0) { // the winners of both sides are the next sub-step's cached planes: one lane of the pair writes the word
+            const unsigned long long nh = hint_word(iO, iQ, jO, jQ, nO, nQ, prim, smax, rsum);
+            gE(E.hint, (int)(cw & ((1u << BP_CC_IDX_BITS) - 1u)) * BP_KADJ + (int)((cw >> BP_CC_IDX_BITS) & 31u)) = nh;
+            if (first_round) L.cc_hw[cw >> 20] = nh;
+        }
+        PROF_ACC(31)
+        {   // support queries for the support vertices that could not be certified: direction -n over A, n over B; the first minimum is the first maximum wanted
+            const unsigned long long mq = ballot(need);
+            const int nq2 = __popcll(mq), sl = popc_below(mq, lane);
+            PROF_CNT(39, nq2)
+            PROF_CNT(53, (unsigned long long)__popcll(mq & 0x5555555555555555ull) | ((unsigned long long)__popcll(mq & 0xAAAAAAAAAAAAAAAAull) << 32))   // queries over A | over B
+            for (int q0 = 0; q0 < nq2; q0 += BP_QCAP) {
+                const bool in = need && sl >= q0 && sl < q0 + BP_QCAP;
+                if (in) { L.q_dir[sl - q0] = vneg(nO_); L.q_meta[sl - q0] = (e.x & 0xFFFFu) | ((unsigned)nO << 16); }
+                lds_sync();
+                support_queries<VL>(E, L, min(nq2 - q0, BP_QCAP));
+                lds_sync();
+                if (in) i1 = (int)L.r_idx[sl - q0];
+                lds_sync();
+            }
+        }
+        PROF_ACC(32)
+        // ContactPoints: the own shape's candidate edges are fetched together, then selected; the own shape's point of both contacts lies on that edge
+        const int a0 = (i1 == 0) ? nO - 1 : i1 - 1, a2 = (i1 + 1 == nO) ? 0 : i1 + 1;
+        const d2 nO1 = gE(E.wn, oO + i1), nO2 = gE(E.wn, oO + a2), vO0 = gE(E.wv, oO + a0), vO1 = gE(E.wv, oO + i1), vO2 = gE(E.wv, oO + a2);
+        const bool fO = vdot(nO_, nO1) > vdot(nO_, nO2);
+        const d2 ea = fO ? vO0 : vO1, eb = fO ? vO1 : vO2;
+        const int eia = fO ? a0 : i1, eib = fO ? i1 : a2;
+        const double d_a = vcross(ea, n), d_b = vcross(eb, n);
+        const double denom = 1.0 / (d_b - d_a + BP_DBL_MIN);
+        const double dQ_a = mate_f64(d_a), dQ_b = mate_f64(d_b);
+        // contact 0 pairs the far end of the other edge with this one on A and the near end on B, contact 1 the other way round
+        const d2 nr = vmul(n, sd ? -rO : rO);
+        const d2 pt0 = vadd(nr, vlerp(ea, eb, clamp01(((sd ? dQ_a : dQ_b) - d_a) * denom)));
+        const d2 pt1 = vadd(nr, vlerp(ea, eb, clamp01(((sd ? dQ_b : dQ_a) - d_a) * denom)));
+        // the lane of A finishes contact 0, the lane of B contact 1: each keeps its own point of that contact and receives the other shape's
+        const d2 ptX = mate_d2(sd ? pt0 : pt1);
+        const d2 p1 = sd ? ptX : pt0, p2 = sd ? pt1 : ptX;
+        const bool hit = touching && vdot(vsub(p2, p1), n) <= 0.0;
+        const int xh = mate_i32((hit ? 1 : 0) | (eib << 1));
+        const bool hitQ = (xh & 1) != 0;
+        const unsigned h = sd ? ((unsigned)(xh >> 1) << 8) | (unsigned)eia : ((unsigned)eia << 8) | (unsigned)(xh >> 1);
+        const bool any = hit || hitQ, two = hit && hitQ;
+        PROF_CNT(54, (unsigned long long)__popcll(ballot(sd == 0 && hit && !hitQ)) | ((unsigned long long)__popcll(ballot(sd == 0 && !hit && hitQ)) << 32))   // one point: the first candidate | the second
+        PROF_CNT(55, __popcll(ballot(sd == 0 && two)))                                                                                                        // two points
+        PROF_ACC(10)
+        // ---- 4c. cpArbiterUpdate: the two lanes write the pair's mailbox entry, the lane that owns the pair's arbiter slot takes it ---------------------
+        const bool flagonly = (cw & (1u << 19)) != 0;
+        if (ballot(any && flagonly)) S.wall_flag = 1;
+        const bool del = any && !flagonly;
+        const unsigned long long dm = ballot(del && sd == 0);
+        const int drank = popc_below(dm, lane & ~1);
+        const int ndel = __popcll(dm);
+        const unsigned keyv = (e.x << 16) | (e.x >> 16);     // on the even lanes: shapeA << 16 | shapeB
+        lds_sync(); // the mailbox aliases the support-query buffers: all reads of them are done
+        for (int dbase = 0; dbase < ndel; dbase += BP_MBOX) {
+            if (del && drank >= dbase && drank < dbase + BP_MBOX) {
+                // entry: n, (p1, p2) of the first contact, of the second, (h0 | count, h1 | 0).  A lone second contact becomes the first.
+                d2 *mb = L.mbox + (drank - dbase) * 6;
+                if (sd == 0) {
+                    mb[0] = n;
+                    if (hit) { mb[1] = p1; mb[2] = p2; mb[5].x = __hiloint2double((int)h, two ? 2 : 1); }
+                } else {
+                    if (!hitQ) { mb[1] = p1; mb[2] = p2; mb[5].x = __hiloint2double((int)h, 1); }
+                    mb[3] = two ? p1 : mk2(0, 0); mb[4] = two ? p2 : mk2(0, 0);
+                    mb[5].y = __hiloint2double(two ? (int)h : 0, 0);
+                }
+            }
+            lds_sync();
+            arbiters_take(E, L, A, S, dm, dbase, keyv, now);
+            lds_sync();
+        }
+    }
+}
+
 // One sub-step.  ship_rules: agent rules applied after the sub-step -- 0 none (reset / settle), 1 the yaw + boundary rules of ShipIceEnv.step
 // (ship_ice_env.py:284-290), 2 the boundary rule alone (MazeNAMO.step, maze_NAMO_env.py:417-419: a maze handle served by a generic KIND 0 instantiation
 // -- damping != 0, hulls above 8 vertices -- must not get the ship's yaw clamp).
@@ -282,6 +509,8 @@ __device__ __forceinline__ void substep(const DevParams &P, const EnvCtx &E, con
     // vertex loops run to the largest hull of the environment family (box-delivery: quads and triangles only; maze: the
     // 8-vertex robot outline, checked at load -- larger outlines use the generic instantiation)
     constexpr int VL = (KIND == BP_ENV_BOX) ? 4 : (KIND == BP_ENV_MAZE) ? 8 : BP_MAXV;
+    // manifold phase with one lane per side of a pair; box-delivery keeps one lane per pair (k_bd_physics sits at the register line and has the event mailbox)
+    constexpr bool ML2 = (BP_MANIFOLD_LANES == 2) && KIND != BP_ENV_BOX;
     if (KIND == BP_ENV_BOX) { S.nev = 0; S.evmask = 0ull; }
     S.stamp += 1u;
     const unsigned now = S.stamp;
@@ -530,6 +759,10 @@ __device__ __forceinline__ void substep(const DevParams &P, const EnvCtx &E, con
             L.pt_thr[myr] = mk2(sepAc, sepBc);
             L.res_smA[myr] = evA ? f64_key(sepAc) : 0ull; L.res_iA[myr] = evA ? ((unsigned)hA << 8) | (unsigned)jAc : 0xFFFFFFFFu;
             L.res_smB[myr] = evB ? f64_key(sepBc) : 0ull; L.res_iB[myr] = evB ? ((unsigned)hB << 8) | (unsigned)jBc : 0xFFFFFFFFu;
+            // what the side lanes of the manifold phase need of the candidate lane and the tables above lack: whose neighbour slot holds the pair's hint word, the pair
+            // filter's flag and this lane (for the candidate cache).  The radii they read where this lane read them.
+            static_assert(BP_CC_IDX_BITS + 5 <= 19 && BP_KADJ <= 32, "candidate lane's word: i | slot << BP_CC_IDX_BITS | flagonly << 19 | lane << 20");
+            if (ML2) L.res_jA[myr] = (unsigned)i | ((unsigned)s << BP_CC_IDX_BITS) | (flagonly ? 1u << 19 : 0u) | ((unsigned)lane << 20);
         }
         lds_sync();
         {
@@ -667,6 +900,8 @@ __device__ __forceinline__ void substep(const DevParams &P, const EnvCtx &E, con
             }
         }
         PROF_ACC(3)
+        // ---- 4b / 4c with one lane per side of a pair (manifold_lanes above); BP_DEBUG_PATHS bit 32 takes the one-lane text below instead ----------------
+        if (ML2 && !BP_DBGP(32)) { manifold_lanes<VL>(P, E, L, A, S, nc, base == 0, now PROF_ARG); continue; }
         // ---- 4b. closest features -> normal -> Chipmunk ContactPoints, one pair per lane ------------------------------
         Manifold M;
         M.count = 0; M.h0 = M.h1 = 0; M.n = mk2(0, 0);
@@ -852,41 +1087,7 @@ __device__ __forceinline__ void substep(const DevParams &P, const EnvCtx &E, con
                 mb[5] = mk2(__hiloint2double((int)M.h0, M.count), __hiloint2double((int)M.h1, 0));
             }
             lds_sync();
-            int my_mb = -1;
-            bool fresh = false;
-            unsigned long long m = dm;
-            int dr = 0;
-            const unsigned keyv = ((unsigned)sa << 16) | (unsigned)sb;
-            while (m) { // every arbiter lane looks for its pair among the delivered ones; a pair nobody owns gets a free slot (rare)
-                const int l = __ffsll((long long)m) - 1;
-                m &= m - 1;
-                if (dr >= dbase && dr < dbase + BP_MBOX) {
-                    const unsigned key = (unsigned)__builtin_amdgcn_readlane((int)keyv, l);
-                    const bool own = (A.key == key);
-                    if (BP_UNLIKELY2(!ballot(own))) {
-                        const unsigned long long om = ballot(A.key == ARB_FREE_KEY);
-                        if (!om) S.err |= BP_ERR_ARB_OVERFLOW;
-                        else {
-                            const int owner = __ffsll((long long)om) - 1;
-                            const int s1 = slot_get(L, S, E.pxy, (int)(key >> 16)), s2 = slot_get(L, S, E.pxy, (int)(key & 0xFFFFu));
-                            if (lane == owner) { my_mb = dr - dbase; fresh = true; A.key = key; A.slotA = s1; A.slotB = s2; }
-                        }
-                    } else if (own) my_mb = dr - dbase;
-                }
-                dr++;
-            }
-            if (my_mb >= 0) {
-                const d2 *mb = L.mbox + my_mb * 6;
-                const d2 mn_ = mb[0], mp10 = mb[1], mp20 = mb[2], mp11 = mb[3], mp21 = mb[4], mh = mb[5];
-                const d2 pa = L.sp[A.slotA], pbp = L.sp[A.slotB];
-                const unsigned mh0 = (unsigned)__double2hiint(mh.x), mh1 = (unsigned)__double2hiint(mh.y);
-                const int mcount = __double2loint(mh.x);
-                if (BP_UNLIKELY2(fresh)) { // masses and material products of a pair stay with its arbiter
-                    const int usa = (int)(A.key >> 16), usb = (int)(A.key & 0xFFFFu);
-                    arbiter_adopt(A, gE(E.mass, usa), gE(E.mass, usb), gE(E.prop, usa), gE(E.prop, usb));
-                }
-                arbiter_update(A, mn_, mp10, mp20, mp11, mp21, mh0, mh1, mcount, pa, pbp, now);
-            }
+            arbiters_take(E, L, A, S, dm, dbase, ((unsigned)sa << 16) | (unsigned)sb, now);
             lds_sync();
         }
     }

@@ -10,11 +10,13 @@ import re
 import sys
 
 # phases of substep() as line ranges of csrc/bp_physics.hpp (update when the file moves; `grep -n "// ---- " csrc/bp_physics.hpp`)
-PH = [(277, 293, '0head'), (294, 367, '1integrate'), (368, 381, '2refresh'), (382, 466, '3candidates'), (467, 516, '4a_cached_planes'),
-      (517, 669, '4a_bound_rounds+search'), (670, 840, '4b_manifold'), (841, 944, '4c_deliver'), (945, 957, '5events+filter'),
-      (958, 974, '6a_prestep'), (975, 1002, '6a_warmset'), (1003, 1042, '6a_colour'), (1043, 1068, '6b_velint'), (1069, 1092, '6c_warmstart'),
-      (1093, 1280, '6d_solver'), (1281, 1335, '7post'), (1336, 1402, '7mvlist'), (242, 266, 'support_queries'), (212, 234, 'world_from_pose'),
-      (159, 209, 'refresh_body')]
+PH = [(504, 522, '0head'), (523, 596, '1integrate'), (597, 610, '2refresh'), (611, 695, '3candidates'), (696, 745, '4a_cached_planes'),
+      (746, 902, '4a_bound_rounds+search'), (903, 904, '4b+4c_side_lanes'), (905, 1075, '4b_manifold'), (1076, 1145, '4c_deliver'), (1146, 1158, '5events+filter'),
+      (1159, 1175, '6a_prestep'), (1176, 1203, '6a_warmset'), (1204, 1243, '6a_colour'), (1244, 1269, '6b_velint'), (1270, 1293, '6c_warmstart'),
+      (1294, 1481, '6d_solver'), (1482, 1536, '7post'), (1537, 1603, '7mvlist'), (250, 275, 'support_queries'), (221, 243, 'world_from_pose'),
+      (168, 218, 'refresh_body'), (278, 316, 'arbiters_take'), (318, 493, 'manifold_lanes')]
+# ('4b+4c_side_lanes' is the call of manifold_lanes(): a block is attributed to the outermost line of its inline chain, so the whole side-lane text, its support
+# queries and its share of arbiters_take() are counted there; the one-lane text below it is compiled for box-delivery and the diagnostic twin only)
 
 
 def phase_of(chain):
