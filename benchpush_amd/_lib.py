@@ -30,7 +30,9 @@ EXPORTS = ["bp_abi_version", "bp_create", "bp_destroy", "bp_load_scenarios", "bp
            "bp_sizeof_render_args", "bp_sizeof_render_prim", "bp_set_render_table", "bp_render",
            "bp_state_bytes", "bp_state_layout_id", "bp_save_state", "bp_load_state", "bp_clone_state", "bp_state_layout_query",
            "bp_sizeof_swath_config", "bp_swath_cost",
-           "bp_sizeof_lattice_config", "bp_lattice_workspace_bytes", "bp_lattice_search"]
+           "bp_sizeof_lattice_config", "bp_lattice_workspace_bytes", "bp_lattice_search",
+           "bp_sizeof_track_config", "bp_track_path"]
+TRACK_NONE, TRACK_GENTLE, TRACK_PID, TRACK_NEAR = 0, 1, 2, 3
 LATTICE_FOUND, LATTICE_NO_PATH, LATTICE_CAP, LATTICE_SKIPPED = 0, 1, 2, 3
 LATTICE_MAX_EDGES = 32   # bp_lattice_search: edges per base heading at most
 SWATH_CLIP, SWATH_REJECT = 0, 1
@@ -53,6 +55,12 @@ class BpLatticeConfig(C.Structure):
                 ("margin", C.c_int32), ("h_baseline", C.c_int32), ("max_expansions", C.c_int32), ("node_capacity", C.c_int32),
                 ("queue_capacity", C.c_int32), ("max_path_nodes", C.c_int32), ("pad_", C.c_int32), ("map_stride", C.c_int64),
                 ("mask_stride", C.c_int64), ("unit", C.c_double), ("weight", C.c_double), ("turning_radius", C.c_double)]
+
+
+class BpTrackConfig(C.Structure):
+    _fields_ = [("P", C.c_int32), ("pad_", C.c_int32)] + [(n, C.c_double) for n in (
+        "thresh", "look_car", "d_back", "d_ahead", "kp", "ki", "kd", "i_cap", "dead", "straight_ang", "yaw_big", "omega_small", "kp_v", "ki_v", "v_max",
+        "omega_max", "dt", "action_scale")]
 
 
 class BpConfig(C.Structure):
@@ -214,6 +222,11 @@ def load():
         L.bp_lattice_workspace_bytes.argtypes = [C.POINTER(BpLatticeConfig), C.c_int32]
         L.bp_lattice_workspace_bytes.restype = C.c_int64
         L.bp_lattice_search.argtypes = [vp, C.POINTER(BpLatticeConfig)] + [vp] * 10 + [C.c_int64] + [vp] * 7
+    if hasattr(L, "bp_track_path"):   # path tracking (absent from older builds loaded for same-box comparisons)
+        L.bp_sizeof_track_config.restype = C.c_int32
+        if L.bp_sizeof_track_config() != C.sizeof(BpTrackConfig):
+            raise BpError("bp_track_config layout mismatch between _lib.BpTrackConfig and the library")
+        L.bp_track_path.argtypes = [vp, C.POINTER(BpTrackConfig), vp, C.c_int64] + [vp] * 8
     _lib = L
     return L
 

@@ -23,6 +23,7 @@
 #include "bp_state.hpp"
 #include "bp_swath.hpp"
 #include "bp_lattice.hpp"
+#include "bp_track.hpp"
 
 struct bp_handle {
     bp_config cfg;
@@ -1369,6 +1370,27 @@ int bp_swath_cost(bp_handle *h, const bp_swath_config *cfg, const double *cost_m
     A.map_stride = cfg->map_stride;
     A.maps = cost_maps; A.paths = paths; A.fp = footprint; A.lengths = lengths; A.rows = rows; A.costs = costs; A.swaths = swaths;
     hipLaunchKernelGGL(k_swath_cost, dim3((unsigned)ncand), dim3(64), (size_t)words * 8, (hipStream_t)stream, A);
+    HIPCHK(h, hipGetLastError());
+    return BP_OK;
+}
+// ---- path tracking ----
+int32_t bp_sizeof_track_config(void) { return (int32_t)sizeof(bp_track_config); }
+int bp_track_path(bp_handle *h, const bp_track_config *cfg, const double *paths, int64_t path_stride, const int32_t *lengths, const double *poses,
+                  const uint8_t *active, double *state, double *actions, double *ct_err, int32_t *diag, void *stream)
+{
+    if (!h) return BP_EINVAL;
+    if (!cfg || !paths || !poses || !state || !actions || !ct_err) return fail(h, BP_EINVAL, "bp_track_path: NULL required pointer");
+    if (!h->loaded || !h->was_reset) return fail(h, BP_ESTATE, "bp_track_path before bp_load_scenarios/bp_reset");
+    if (h->P.env_kind != BP_ENV_SHIP_ICE) return fail(h, BP_EINVAL, "bp_track_path: ship-ice handles only");
+    if (cfg->P <= 0 || (long long)cfg->P * 3 > 0x7FFFFFFFll) return fail(h, BP_EINVAL, "bp_track_path: P must be positive (and 3 * P below 2^31)");
+    if (path_stride < 0 || (path_stride > 0 && path_stride < 3ll * cfg->P)) return fail(h, BP_EINVAL, "bp_track_path: bad path_stride");
+    if (!(cfg->dt > 0.0) || !std::isfinite(cfg->dt) || !(cfg->action_scale > 0.0) || !std::isfinite(cfg->action_scale))
+        return fail(h, BP_EINVAL, "bp_track_path: dt and action_scale must be positive and finite");
+    BP_DEVICE(h);
+    TrackArgs A;
+    A.c = *cfg; A.path_stride = path_stride; A.paths = paths; A.poses = poses; A.lengths = lengths; A.active = active;
+    A.state = state; A.actions = actions; A.ct_err = ct_err; A.diag = diag;
+    hipLaunchKernelGGL(k_track_path, dim3((unsigned)h->num_envs), dim3(64), 0, (hipStream_t)stream, A);
     HIPCHK(h, hipGetLastError());
     return BP_OK;
 }

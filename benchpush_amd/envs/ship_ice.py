@@ -456,6 +456,61 @@ class BatchedShipIceEnv(_BatchedBase):
             _ptr(out.n_nodes), _ptr(out.nodes), _ptr(out.edges), self._stream()), "bp_lattice_search")
         return out
 
+    def track_paths(self, paths, state, lengths=None, poses=None, active=None, config=None, out=None):
+        """The tracking controller of the reference's planning-based policy (``PlanningBasedPolicy.act``, policy.py:61-172) for every env in one launch
+        (bp_track_path), no host synchronisation.  DESIGN.md "Path tracking" states the semantics.  All tensors are contiguous and on the env's device:
+
+        paths    float64 [E, P, 3] = (x, y, theta), or one [P, 3] path shared by all envs, in the units of the poses (the reference: metres)
+        state    ``planning.TrackerState`` or its float64 [E, 4] tensor: the integrators, read and written
+        lengths  int32 [E] or None (all P): the samples that count
+        poses    float64 [E, 3] or None: the ships' (x, y, yaw); None takes info[:, :3]
+        active   bool / uint8 [E] or None: envs with False have nothing written
+        config   ``planning.TrackerConfig`` or None (the reference's values); its action_scale defaults to max_yaw_rate_step
+        out      None or (actions float64 [E, 2], ct_err float64 [E], diag int32 [E, 4]) to be overwritten
+
+        Returns (actions, ct_err, diag): actions[:, 0] is the yaw action that ``step`` takes, actions[:, 1] the surge command (which ship-ice-v0 has no
+        use for); diag = (i_near, branch, forward index, backward index) with branch 0 none, 1 gentle fixed-rate turn, 2 PID, 3 near.  An env that is not
+        active or whose length is below 1 has nothing written (fresh outputs are zero), its state row included; a non-finite pose or counted sample
+        gives NaN actions, branch 0 and an untouched state row.  Raises ValueError, before any launch, for a wrong dtype, device, shape or a
+        non-contiguous tensor; BpError for what the library refuses.  Touches no environment state."""
+        from ..planning import TrackerConfig
+        E = self.num_envs
+
+        def need(t, name, dtypes, shapes):
+            dtypes = dtypes if isinstance(dtypes, tuple) else (dtypes,)
+            if not isinstance(t, torch.Tensor) or t.dtype not in dtypes or t.device != self.device or not t.is_contiguous():
+                raise ValueError("track_paths: %s must be a contiguous %s tensor on %s" % (name, " / ".join(map(str, dtypes)), self.device))
+            if not any(len(sh) == t.dim() and all(a is None or a == b for a, b in zip(sh, t.shape)) for sh in shapes):
+                raise ValueError("track_paths: %s has shape %s, expected %s" % (name, tuple(t.shape), " or ".join(str(list(sh)) for sh in shapes)))
+
+        need(paths, "paths", torch.float64, [(E, None, 3), (None, 3)])
+        P = int(paths.shape[-2])
+        st = getattr(state, "state", state)
+        need(st, "state", torch.float64, [(E, 4)])
+        if lengths is not None:
+            need(lengths, "lengths", torch.int32, [(E,)])
+        if poses is None:
+            poses = self.info[:, :3].contiguous()
+        need(poses, "poses", torch.float64, [(E, 3)])
+        if active is not None:
+            need(active, "active", (torch.bool, torch.uint8), [(E,)])
+        actions, ct_err, diag = out if out is not None else (None, None, None)
+        if out is not None:
+            need(actions, "out[0]", torch.float64, [(E, 2)])
+            need(ct_err, "out[1]", torch.float64, [(E,)])
+            need(diag, "out[2]", torch.int32, [(E, 4)])
+        else:
+            actions = torch.zeros((E, 2), dtype=torch.float64, device=self.device)
+            ct_err = torch.zeros(E, dtype=torch.float64, device=self.device)
+            diag = torch.zeros((E, 4), dtype=torch.int32, device=self.device)
+        config = config or TrackerConfig()
+        cfg = _lib.BpTrackConfig(P=P, pad_=0, action_scale=self.max_yaw_rate_step if config.action_scale is None else config.action_scale,
+                                 **config.as_dict())
+        _lib.check(self.L, self.h, self.L.bp_track_path(self.h, C.byref(cfg), _ptr(paths), 3 * P if paths.dim() == 3 else 0, _ptr(lengths), _ptr(poses),
+                                                        _ptr(active), _ptr(st), _ptr(actions), _ptr(ct_err), _ptr(diag), self._stream()),
+                   "bp_track_path")
+        return actions, ct_err, diag
+
     def episode_metrics(self):
         """On-device ShipIceMetric: (rows [E, 6] float64 = efficiency, effort, episode reward, success, episode length, total_work of
         each env's most recently finished episode; counts [E] int32 = episodes finished so far).  Device tensors; rows of envs with

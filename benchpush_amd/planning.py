@@ -3,7 +3,9 @@
 Plain torch / numpy, not a hot path: the footprint of the reference's ``Ship`` (common/ship.py:18-20), constant-curvature candidate paths in closed
 form, the replanning comparison of ``Path.update`` (common/utils/utils.py:58-89), and what the lattice A* (``BatchedShipIceEnv.lattice_search``)
 takes and gives: the primitive tables (``LatticePrimitives``, common/primitives.py), the swath masks (``lattice_swath_masks``, common/swath.py:15-88) and
-the sampled path of a search result (``lattice_full_paths``, ``AStar.build_path``).
+the sampled path of a search result (``lattice_full_paths``, ``AStar.build_path``).  ``BatchedLatticePlanner`` chains them into the planning round of
+``LatticePlanner.plan``.  For ``BatchedShipIceEnv.track_paths``: the controller's tunables and integrators (``TrackerConfig``, ``TrackerState``) and the
+reference's ``straight_planner`` for a batch (``straight_paths``).
 """
 import numpy as np
 import torch
@@ -11,7 +13,7 @@ import torch
 from . import dubins as _dubins
 
 __all__ = ["ship_footprint", "arc_paths", "replan_mask", "LATTICE_SHIP_VERTICES", "LatticePrimitives", "ship_halves", "lattice_max_val",
-           "lattice_swath_masks", "lattice_full_paths"]
+           "lattice_swath_masks", "lattice_full_paths", "BatchedLatticePlanner", "TrackerConfig", "TrackerState", "straight_paths"]
 
 # ship.vertices of the reference's lattice planner configuration (17 vertices, some collinear); with padding 0.25 and scale 5 it is the planner's footprint
 LATTICE_SHIP_VERTICES = [[1., -0.], [0.9, 0.10], [0.5, 0.25], [0.25, 0.25], [0, 0.25], [-0.25, 0.25], [-0.5, 0.25], [-0.75, 0.25], [-1., 0.25],
@@ -247,3 +249,152 @@ def lattice_full_paths(prims, result, starts):
     out = torch.zeros((E, Pmax + 1, 3), dtype=torch.float64, device=dev)
     out.scatter_(1, dst.reshape(E, -1, 1).expand(E, (N - 1) * Pm, 3), torch.stack([x, y, t], -1).reshape(E, -1, 3))
     return out[:, :Pmax].contiguous(), ns.sum(1).to(torch.int32)
+
+
+class BatchedLatticePlanner:
+    """The planning round of the reference's ``LatticePlanner.plan`` (baselines/ship_ice_nav/planning_based/planners/lattice.py) for every env of a
+    ``BatchedShipIceEnv`` at once, with no host synchronisation: cost maps -> lattice A* from each ship's pose to the horizon's goal line -> the sampled
+    path of each node path -> ``Path.update``'s comparison of the new and the kept path over the same row window.
+
+    prims    ``LatticePrimitives``: the control set is data that the caller passes
+    scale, padding, horizon: cells per metre, footprint padding and receding horizon in metres (the reference's lattice_config.yaml: 5, 0.25, 30)
+
+    ``path`` [E, Pmax, 3] and ``lengths`` [E] hold the kept paths in cost-map cells (None before the first round); ``status`` the last search's status and
+    ``found`` the number of searches that found a path so far (device tensors)."""
+
+    def __init__(self, env, prims, scale=5, padding=0.25, horizon=30, ship_vertices=None, threshold_cost=0.95, search_kwargs=None):
+        self.env, self.prims = env, prims
+        self.scale, self.padding, self.horizon, self.threshold_cost = scale, padding, horizon, threshold_cost
+        self.fp_np = ship_footprint(LATTICE_SHIP_VERTICES if ship_vertices is None else ship_vertices, scale, padding)
+        self.fp = torch.from_numpy(self.fp_np).to(env.device)
+        self.search_kwargs = dict(search_kwargs or {})
+        self.path = self.lengths = self.status = None
+        self.found = torch.zeros((), dtype=torch.int64, device=env.device)
+
+    def pose_cells(self):
+        """The ships' poses in cost-map cells: [E, 3] float64."""
+        return self.env.info[:, :3] * torch.tensor([self.scale, self.scale, 1.0], dtype=torch.float64, device=self.env.device)
+
+    def plan(self, fresh=None, update=True):
+        """One planning round; returns the kept paths [E, P, 3] and their lengths [E] (device tensors).  fresh: bool / uint8 [E] or None: envs that take
+        their new path unconditionally, found or not (an episode start).  The other envs apply ``Path.update``'s comparison if `update`, else they keep
+        their path and are not searched.  The first round takes every new path."""
+        env, cfg, scale = self.env, self.env.cfg, self.scale
+        m, n = int(cfg.occ.map_height), int(cfg.occ.map_width)
+        pose = self.pose_cells()
+        first = self.path is None
+        if fresh is not None:
+            fresh = fresh.to(device=env.device, dtype=torch.bool).contiguous()
+        half = float(self.fp_np[:, 0].max() - self.fp_np[:, 0].min()) / 2
+        maps = env.cost_maps(scale, m, n, horizon=self.horizon, ship_pos_y=pose[:, 1] - half, vs=float(cfg.target_speed) * scale + 1e-8)
+        goal_y = torch.clamp(pose[:, 1] + self.horizon * scale, max=float(cfg.goal_y) * scale).contiguous()
+        masks = lattice_swath_masks(env, self.prims, self.fp_np, pose[:, 2])
+        active = fresh if (fresh is not None and not update and not first) else None
+        res = env.lattice_search(maps, pose.contiguous(), goal_y, self.prims, masks, active=active, **self.search_kwargs)
+        res.n_nodes = torch.where(res.status == 0, res.n_nodes, torch.zeros_like(res.n_nodes))   # only found envs have their rows written
+        new, new_len = lattice_full_paths(self.prims, res, pose)
+        self.status = res.status
+        self.found += (res.status == 0).sum()
+        if first:
+            self.path, self.lengths = new, new_len
+            return self.path, self.lengths
+        if update:
+            # Path.update: both swath costs over the rows from the ship to the goal line
+            rows = torch.stack([pose[:, 1].to(torch.int32), goal_y.to(torch.int32)], 1).contiguous()
+            both = torch.stack([new, self.path], 1).contiguous()
+            cost = env.swath_costs(both, self.fp, maps, lengths=torch.stack([new_len, self.lengths], 1).contiguous(), rows=rows)
+            take = (new_len > 0) & (replan_mask(cost[:, 0], cost[:, 1], self.threshold_cost) | (self.lengths == 0))
+            if fresh is not None:
+                take = take | fresh
+        else:
+            take = fresh if fresh is not None else torch.zeros_like(new_len, dtype=torch.bool)
+        self.path = torch.where(take[:, None, None], new, self.path)
+        self.lengths = torch.where(take, new_len, self.lengths)
+        return self.path, self.lengths
+
+    def paths_metres(self):
+        """The kept paths in metres, [E, P, 3] contiguous: what ``track_paths`` takes next to the env's own poses."""
+        return (self.path / torch.tensor([self.scale, self.scale, 1.0], dtype=torch.float64, device=self.env.device)).contiguous()
+
+    def pursuit_actions(self, lookahead=15.0):
+        """A plain pure-pursuit rule over the kept path (`lookahead` cells ahead of the ship): yaw actions [E] in [-1, 1].  Not the reference's
+        controller: that is ``BatchedShipIceEnv.track_paths``."""
+        dev = self.env.device
+        pose = self.pose_cells()
+        P = self.path.shape[1]
+        valid = torch.arange(P, device=dev)[None, :] < self.lengths[:, None]
+        d = torch.hypot(self.path[:, :, 0] - pose[:, None, 0], self.path[:, :, 1] - pose[:, None, 1])
+        ahead = valid & (d >= lookahead) & (self.path[:, :, 1] > pose[:, None, 1])
+        idx = torch.where(ahead.any(1), ahead.to(torch.int64).argmax(1), (self.lengths.to(torch.int64) - 1).clamp_min(0))
+        tgt = self.path[torch.arange(self.path.shape[0], device=dev), idx]
+        bearing = torch.atan2(tgt[:, 1] - pose[:, 1], tgt[:, 0] - pose[:, 0])
+        err = torch.remainder(bearing - pose[:, 2] + torch.pi, 2 * torch.pi) - torch.pi
+        return torch.where(self.lengths > 0, (2.0 * err).clamp(-1.0, 1.0), torch.zeros_like(err))
+
+
+class TrackerConfig:
+    """The tunables of the reference's tracking controller (``PlanningBasedPolicy.act``, policy.py:63-82) as data; the defaults are the reference's values.
+    They are in the units of the paths and poses that ``track_paths`` is given (the reference: metres).  action_scale None: the env's max_yaw_rate_step."""
+    FIELDS = ("thresh", "look_car", "d_back", "d_ahead", "kp", "ki", "kd", "i_cap", "dead", "straight_ang", "yaw_big", "omega_small", "kp_v", "ki_v",
+              "v_max", "omega_max", "dt")
+
+    def __init__(self, thresh=10.0, look_car=50.0, d_back=15.0, d_ahead=25.0, kp=0.10, ki=0.15, kd=2.0, i_cap=10.0, dead=0.02, straight_ang=0.100,
+                 yaw_big=0.50, omega_small=0.002, kp_v=0.50, ki_v=0.05, v_max=2.5, omega_max=0.02, dt=0.005, action_scale=None):
+        for k, v in list(locals().items()):
+            if k in self.FIELDS:
+                setattr(self, k, float(v))
+        self.action_scale = None if action_scale is None else float(action_scale)
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k in self.FIELDS}
+
+
+class TrackerState:
+    """The integrators that the controller keeps between calls: ``state`` float64 [E, 4] = (int_yaw, prev_yaw, int_v, has_yaw) on the device.  A zero row
+    is a fresh controller."""
+
+    def __init__(self, num_envs=None, device="cuda:0", state=None):
+        self.state = torch.zeros((int(num_envs), 4), dtype=torch.float64, device=device) if state is None else state
+
+    def reset(self, mask=None):
+        """Fresh controllers for the envs of `mask` (bool / uint8 [E]; None: all).  No host synchronisation."""
+        if mask is None:
+            self.state.zero_()
+        else:
+            self.state.masked_fill_(mask.to(device=self.state.device, dtype=torch.bool)[:, None], 0.0)
+        return self
+
+    def clone(self):
+        return TrackerState(state=self.state.clone())
+
+    def to(self, device):
+        return TrackerState(state=self.state.to(device))
+
+
+def straight_paths(pose, goal_y, dy=10, max_len=None):
+    """The reference's ``straight_planner`` (policy.py:44-59) for a batch: from every pose [E, 3] = (x, y, theta) the samples (x, y + i * dy, theta) up to
+    goal_y (a number or [E]), goal_y itself included where it lands on the grid -- ``np.arange(y, goal_y + dy * 0.5, dy)`` value for value.  Returns
+    (paths [E, P, 3] float64, lengths [E] int32) on pose's device; rows beyond an env's length repeat nothing meaningful (zeros).  max_len None: P is
+    the longest length, which is read back from the device once; with max_len given nothing is read back and longer paths are cut to it."""
+    pose = torch.as_tensor(pose, dtype=torch.float64)
+    if pose.dim() != 2 or pose.shape[1] != 3:
+        raise ValueError("straight_paths: pose must be [E, 3]")
+    if not dy > 0:
+        raise ValueError("straight_paths: dy must be positive")
+    E, dev = pose.shape[0], pose.device
+    gy = torch.as_tensor(goal_y, dtype=torch.float64).to(dev).expand(E)
+    x, y, th = pose[:, 0], pose[:, 1], pose[:, 2]
+    n = torch.ceil(((gy + dy * 0.5) - y) / dy).clamp(min=0)
+    n = torch.where(torch.isfinite(n), n, torch.zeros_like(n)).to(torch.int64)
+    P = max(1, int(n.max()) if E else 1) if max_len is None else int(max_len)
+    if P <= 0:
+        raise ValueError("straight_paths: max_len must be positive")
+    n = n.clamp(max=P)
+    i = torch.arange(P, dtype=torch.float64, device=dev)[None, :]
+    nxt = y + dy
+    yv = y[:, None] + i * (nxt - y)[:, None]           # numpy fills a float arange as start + i * ((start + step) - start)
+    if P > 1:
+        yv[:, 1] = nxt
+    valid = (torch.arange(P, device=dev)[None, :] < n[:, None])[:, :, None]
+    out = torch.stack([x[:, None].expand(E, P), yv, th[:, None].expand(E, P)], dim=-1)
+    return torch.where(valid, out, torch.zeros_like(out)).contiguous(), n.to(torch.int32)

@@ -504,6 +504,39 @@ int bp_lattice_search(bp_handle *h, const bp_lattice_config *cfg, const double *
                       const uint64_t *masks, void *workspace, int64_t workspace_bytes, int32_t *status, double *g, int32_t *expanded, int32_t *n_nodes,
                       double *nodes, int32_t *edges, void *stream);
 
+/* ---- tracking planned paths ----
+ * The controller of the reference's planning-based policy (PlanningBasedPolicy.act, baselines/ship_ice_nav/planning_based/policy.py:61-172) for every
+ * env in one launch, one wavefront per env (DESIGN.md "Path tracking" states the semantics exactly; tests/track_ref.py restates them).  Device memory:
+ *   paths    double [E][P][3]: samples (x, y, theta) with path_stride doubles between the envs' paths, or one [P][3] path for all envs with path_stride 0
+ *   lengths  int32 [E] or NULL (all P): samples that count, at most P
+ *   poses    double [E][3] = (x, y, yaw) of the ship, in the units of the paths
+ *   active   uint8 [E] or NULL (all)
+ *   state    double [E][4] = (int_yaw, prev_yaw, int_v, has_yaw): the integrators that the controller keeps between calls, read and written; has_yaw is
+ *            0.0 until the PID branch has run once (the reference's hasattr test), then 1.0.  A zeroed row is a fresh controller.
+ *   actions  double [E][2] = (omega / action_scale, 20 * v_cmd): the yaw action of bp_step and the surge command
+ *   ct_err   double [E]: distance to the nearest counted sample
+ *   diag     int32 [E][4] or NULL = (i_near, branch, forward index, backward index); branch BP_TRACK_NONE 0, BP_TRACK_GENTLE 1 (fixed-rate turn),
+ *            BP_TRACK_PID 2, BP_TRACK_NEAR 3.  The forward index is the carrot's in branches 1 and 2 and the end of the slice ahead in branch 3.
+ * An env with active == 0 or a length below 1 has nothing written, its state row included.  A non-finite component in the pose or in a counted sample:
+ * NaN actions and ct_err, diag (-1, 0, -1, -1), the state row untouched.
+ * BP_EINVAL, with nothing launched or written, for a NULL required pointer, P <= 0, 0 < path_stride < 3 * P or a negative one, dt or action_scale that
+ * is not positive and finite, or a handle that is not ship-ice; BP_ESTATE before load and reset.  Reads the handle's device and size only: no environment
+ * state is touched.  Enqueued on `stream`; a function of its inputs bit for bit. */
+enum { BP_TRACK_NONE = 0, BP_TRACK_GENTLE = 1, BP_TRACK_PID = 2, BP_TRACK_NEAR = 3 };
+typedef struct bp_track_config {
+    int32_t P;                                      /* samples per path */
+    int32_t pad_;
+    double thresh, look_car, d_back, d_ahead;       /* cross-track switch (10); carrot distance when far (50); slice behind (15) and ahead (25) */
+    double kp, ki, kd, i_cap, dead;                 /* yaw-rate PID: 0.10, 0.15, 2.0; integrator cap 10; dead zone 0.02 */
+    double straight_ang, yaw_big, omega_small;      /* straight-slice turn: 0.100, 0.50, 0.002 */
+    double kp_v, ki_v, v_max, omega_max;            /* surge PI: 0.50, 0.05, 2.5; yaw-rate cap 0.02 */
+    double dt;                                      /* 0.005 */
+    double action_scale;                            /* the env's max_yaw_rate_step */
+} bp_track_config;
+int32_t bp_sizeof_track_config(void);
+int bp_track_path(bp_handle *h, const bp_track_config *cfg, const double *paths, int64_t path_stride, const int32_t *lengths, const double *poses,
+                  const uint8_t *active, double *state, double *actions, double *ct_err, int32_t *diag, void *stream);
+
 const char *bp_last_error(const bp_handle *h);
 int32_t bp_abi_version(void);
 int32_t bp_sizeof_config(void);   /* sizeof(bp_config), so a binding can verify its struct layout */
