@@ -31,7 +31,10 @@ EXPORTS = ["bp_abi_version", "bp_create", "bp_destroy", "bp_load_scenarios", "bp
            "bp_state_bytes", "bp_state_layout_id", "bp_save_state", "bp_load_state", "bp_clone_state", "bp_state_layout_query",
            "bp_sizeof_swath_config", "bp_swath_cost",
            "bp_sizeof_lattice_config", "bp_lattice_workspace_bytes", "bp_lattice_search",
-           "bp_sizeof_track_config", "bp_track_path"]
+           "bp_sizeof_track_config", "bp_track_path",
+           "bp_sizeof_rrt_config", "bp_rrt_workspace_bytes", "bp_rrt_uniform", "bp_rrt_plan", "bp_sizeof_track_wp_config", "bp_track_waypoints"]
+RRT_FOUND, RRT_FOUND_IGNORING_BOXES, RRT_FALLBACK, RRT_BLOCKED, RRT_CAP, RRT_BAD_INPUT, RRT_SKIPPED = range(7)
+RRT_MAX_WALLS, RRT_MAX_BOX_VERTS = 128, 1280   # bp_rrt_plan: walls, and box slots times vertices per slot, at most
 TRACK_NONE, TRACK_GENTLE, TRACK_PID, TRACK_NEAR = 0, 1, 2, 3
 LATTICE_FOUND, LATTICE_NO_PATH, LATTICE_CAP, LATTICE_SKIPPED = 0, 1, 2, 3
 LATTICE_MAX_EDGES = 32   # bp_lattice_search: edges per base heading at most
@@ -61,6 +64,15 @@ class BpTrackConfig(C.Structure):
     _fields_ = [("P", C.c_int32), ("pad_", C.c_int32)] + [(n, C.c_double) for n in (
         "thresh", "look_car", "d_back", "d_ahead", "kp", "ki", "kd", "i_cap", "dead", "straight_ang", "yaw_big", "omega_small", "kp_v", "ki_v", "v_max",
         "omega_max", "dt", "action_scale")]
+
+
+class BpRrtConfig(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("step", "goal_radius", "goal_bias", "densify_ds", "prune_min_dist", "inflate_radius")] + [
+        ("seed", C.c_uint64), ("max_nodes", C.c_int32), ("max_waypoints", C.c_int32), ("passes", C.c_int32), ("pad_", C.c_int32)]
+
+
+class BpTrackWpConfig(C.Structure):
+    _fields_ = [("P", C.c_int32), ("pad_", C.c_int32), ("Lfc", C.c_double), ("dt", C.c_double), ("action_scale", C.c_double)]
 
 
 class BpConfig(C.Structure):
@@ -227,6 +239,17 @@ def load():
         if L.bp_sizeof_track_config() != C.sizeof(BpTrackConfig):
             raise BpError("bp_track_config layout mismatch between _lib.BpTrackConfig and the library")
         L.bp_track_path.argtypes = [vp, C.POINTER(BpTrackConfig), vp, C.c_int64] + [vp] * 8
+    if hasattr(L, "bp_rrt_plan"):   # batched RRT and its waypoint controller (absent from older builds loaded for same-box comparisons)
+        L.bp_sizeof_rrt_config.restype = C.c_int32
+        L.bp_sizeof_track_wp_config.restype = C.c_int32
+        if L.bp_sizeof_rrt_config() != C.sizeof(BpRrtConfig) or L.bp_sizeof_track_wp_config() != C.sizeof(BpTrackWpConfig):
+            raise BpError("bp_rrt_config / bp_track_wp_config layout mismatch between _lib and the library")
+        L.bp_rrt_workspace_bytes.argtypes = [C.POINTER(BpRrtConfig), C.c_int32]
+        L.bp_rrt_workspace_bytes.restype = C.c_int64
+        L.bp_rrt_uniform.argtypes = [C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32]
+        L.bp_rrt_uniform.restype = C.c_double
+        L.bp_rrt_plan.argtypes = [vp, C.POINTER(BpRrtConfig), vp, vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_int64] + [vp] * 6
+        L.bp_track_waypoints.argtypes = [vp, C.POINTER(BpTrackWpConfig)] + [vp] * 7
     _lib = L
     return L
 

@@ -24,6 +24,7 @@
 #include "bp_swath.hpp"
 #include "bp_lattice.hpp"
 #include "bp_track.hpp"
+#include "bp_rrt.hpp"
 
 struct bp_handle {
     bp_config cfg;
@@ -1391,6 +1392,84 @@ int bp_track_path(bp_handle *h, const bp_track_config *cfg, const double *paths,
     A.c = *cfg; A.path_stride = path_stride; A.paths = paths; A.poses = poses; A.lengths = lengths; A.active = active;
     A.state = state; A.actions = actions; A.ct_err = ct_err; A.diag = diag;
     hipLaunchKernelGGL(k_track_path, dim3((unsigned)h->num_envs), dim3(64), 0, (hipStream_t)stream, A);
+    HIPCHK(h, hipGetLastError());
+    return BP_OK;
+}
+// ---- batched RRT and the waypoint controller ----
+int32_t bp_sizeof_rrt_config(void) { return (int32_t)sizeof(bp_rrt_config); }
+int32_t bp_sizeof_track_wp_config(void) { return (int32_t)sizeof(bp_track_wp_config); }
+double bp_rrt_uniform(uint64_t seed, int64_t stream, int32_t pass, int32_t iteration, int32_t draw)
+{
+    return bp_rrt_u01(seed, stream, pass, iteration, draw);
+}
+static const char *rrt_config_error(const bp_rrt_config *c)
+{
+    const double v[6] = {c->step, c->goal_radius, c->goal_bias, c->densify_ds, c->prune_min_dist, c->inflate_radius};
+    for (double x : v) if (!std::isfinite(x) || x < 0.0) return "bp_rrt_plan: a config value is negative or not finite";
+    if (!(c->step > 0.0)) return "bp_rrt_plan: step must be positive";
+    if (c->max_nodes < 1 || c->max_nodes > 0x3FFFFFFF) return "bp_rrt_plan: max_nodes must be 1 .. 2^30 - 1";
+    if (c->max_waypoints < 2 || c->max_waypoints > 0x3FFFFFFF) return "bp_rrt_plan: max_waypoints must be at least 2";
+    if (c->passes < 1 || c->passes > 2) return "bp_rrt_plan: passes must be 1 or 2";
+    if (!(((double)c->max_nodes + 2.0) * std::fmax(1.0, std::fmax(c->step, c->goal_radius) / std::fmax(1e-3, c->densify_ds)) <= RRT_DENSE_POINTS_MAX))
+        return "bp_rrt_plan: (max_nodes + 2) * max(1, max(step, goal_radius) / max(1e-3, densify_ds)) exceeds 2^22 dense points";
+    return nullptr;
+}
+static long long rrt_per_env(const bp_rrt_config *c) { return (((long long)c->max_nodes + 2) * 20 + 15) & ~15ll; }
+int64_t bp_rrt_workspace_bytes(const bp_rrt_config *cfg, int32_t num_envs)
+{
+    if (!cfg || num_envs <= 0 || rrt_config_error(cfg)) return BP_EINVAL;
+    return (int64_t)(rrt_per_env(cfg) * num_envs);
+}
+int bp_rrt_plan(bp_handle *h, const bp_rrt_config *cfg, const double *starts, const double *goals, const double *walls, int32_t n_walls,
+                const double *boxes, const int32_t *counts, int32_t n_boxes, int32_t n_verts, const int64_t *streams, const uint8_t *active,
+                void *workspace, int64_t workspace_bytes, int32_t *status, int32_t *n_nodes, int32_t *iterations, double *paths, int32_t *lengths,
+                void *stream)
+{
+    if (!h) return BP_EINVAL;
+    if (!cfg || !starts || !goals || !streams || !workspace || !status || !n_nodes || !iterations || !paths || !lengths)
+        return fail(h, BP_EINVAL, "bp_rrt_plan: NULL required pointer");
+    if (!h->loaded || !h->was_reset) return fail(h, BP_ESTATE, "bp_rrt_plan before bp_load_maze/bp_reset");
+    if (h->P.env_kind != BP_ENV_MAZE) return fail(h, BP_EINVAL, "bp_rrt_plan: maze handles only");
+    if (const char *e = rrt_config_error(cfg)) return fail(h, BP_EINVAL, e);
+    if (n_walls < 0 || n_walls > BP_RRT_MAX_WALLS || (n_walls > 0 && !walls)) return fail(h, BP_EINVAL, "bp_rrt_plan: n_walls outside 0 .. BP_RRT_MAX_WALLS");
+    if (n_boxes < 0 || (n_boxes > 0 && (n_verts < 3 || n_verts > BP_MAXV || !boxes || !counts)) || (long long)n_boxes * n_verts > BP_RRT_MAX_BOX_VERTS)
+        return fail(h, BP_EINVAL, "bp_rrt_plan: n_verts outside 3 .. BP_MAXV or n_boxes * n_verts above BP_RRT_MAX_BOX_VERTS");
+    const long long per_env = rrt_per_env(cfg);
+    if (workspace_bytes < per_env * (long long)h->num_envs || (((uintptr_t)workspace) & 15u))
+        return fail(h, BP_EINVAL, "bp_rrt_plan: workspace smaller than bp_rrt_workspace_bytes or not 16-byte aligned");
+    BP_DEVICE(h);
+    RrtArgs A;
+    A.c = *cfg; A.W = n_walls; A.B = n_boxes; A.V = n_boxes > 0 ? n_verts : 0; A.ws_per_env = per_env;
+    A.starts = starts; A.goals = goals; A.walls = walls; A.boxes = boxes; A.counts = counts; A.streams = (const long long *)streams; A.active = active;
+    A.ws = (char *)workspace; A.status = status; A.n_nodes = n_nodes; A.iterations = iterations; A.lengths = lengths; A.paths = paths;
+    // BP_RRT_LDS_NODES (read at every call; default RRT_LDS_NODES_DEFAULT) is how many of the tree's first nodes the nearest search keeps in LDS: a
+    // multiple of 64, at most 2048, 0 for none.  It changes the time of a launch, not the plan (profiles/rrt/README.md)
+    int lds_nodes = RRT_LDS_NODES_DEFAULT;
+    if (const char *e = getenv("BP_RRT_LDS_NODES")) lds_nodes = atoi(e);
+    lds_nodes = lds_nodes < 0 ? 0 : (lds_nodes > 2048 ? 2048 : lds_nodes & ~63);
+    lds_nodes = std::min(lds_nodes, (cfg->max_nodes + 2 + 63) & ~63);
+    const size_t lds_scene = (size_t)(A.W + A.B * A.V) * 32 + (size_t)(A.B + (A.B & 1)) * 8;     // at most 45056 + 3416 bytes
+    lds_nodes = std::min(lds_nodes, (int)((65536 - lds_scene) / 16) & ~63);                       // 64 KB of LDS per workgroup at most
+    A.lds_nodes = lds_nodes;
+    const size_t lds = lds_scene + (size_t)lds_nodes * 16;
+    hipLaunchKernelGGL(k_rrt_plan, dim3((unsigned)h->num_envs), dim3(64), lds, (hipStream_t)stream, A);
+    HIPCHK(h, hipGetLastError());
+    return BP_OK;
+}
+int bp_track_waypoints(bp_handle *h, const bp_track_wp_config *cfg, const double *paths, const int32_t *lengths, const double *poses,
+                       const uint8_t *active, double *actions, int32_t *diag, void *stream)
+{
+    if (!h) return BP_EINVAL;
+    if (!cfg || !paths || !poses || !actions || !diag) return fail(h, BP_EINVAL, "bp_track_waypoints: NULL required pointer");
+    if (!h->loaded || !h->was_reset) return fail(h, BP_ESTATE, "bp_track_waypoints before bp_load_maze/bp_reset");
+    if (h->P.env_kind != BP_ENV_MAZE) return fail(h, BP_EINVAL, "bp_track_waypoints: maze handles only");
+    if (cfg->P <= 0 || (long long)cfg->P * 2 > 0x7FFFFFFFll) return fail(h, BP_EINVAL, "bp_track_waypoints: P must be positive (and 2 * P below 2^31)");
+    if (!std::isfinite(cfg->Lfc) || !(cfg->dt > 0.0) || !std::isfinite(cfg->dt) || !(cfg->action_scale > 0.0) || !std::isfinite(cfg->action_scale))
+        return fail(h, BP_EINVAL, "bp_track_waypoints: Lfc must be finite, dt and action_scale positive and finite");
+    BP_DEVICE(h);
+    TrackWpArgs A;
+    A.c = *cfg; A.paths = paths; A.lengths = lengths; A.poses = poses; A.active = active; A.actions = actions; A.diag = diag;
+    hipLaunchKernelGGL(k_track_waypoints, dim3((unsigned)h->num_envs), dim3(64), 0, (hipStream_t)stream, A);
     HIPCHK(h, hipGetLastError());
     return BP_OK;
 }

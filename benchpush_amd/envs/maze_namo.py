@@ -95,6 +95,130 @@ class BatchedMazeEnv(BatchedShipIceEnv):
         _lib.check(self.L, self.h, self.L.bp_get_goal_map(self.h, out.ctypes.data_as(C.c_void_p), None, None), "bp_get_goal_map")
         return out
 
+    # -- the planning baseline's device calls (DESIGN.md "RRT") ---------------------------------------------
+    def _need(self, fn, t, name, dtypes, shape):
+        dtypes = dtypes if isinstance(dtypes, tuple) else (dtypes,)
+        if not isinstance(t, torch.Tensor) or t.dtype not in dtypes or t.device != self.device or not t.is_contiguous():
+            raise ValueError("%s: %s must be a contiguous %s tensor on %s" % (fn, name, " / ".join(map(str, dtypes)), self.device))
+        if t.dim() != len(shape) or any(a is not None and a != b for a, b in zip(shape, t.shape)):
+            raise ValueError("%s: %s has shape %s, expected %s" % (fn, name, tuple(t.shape), list(shape)))
+
+    def box_polys(self):
+        """The box rows of ``world_polys()``: (verts [E, nbox, 20, 2] f64, counts [E, nbox] i32), contiguous."""
+        verts, cnt = self.world_polys()
+        n0 = 1 + len(self.cfg.robot.wheel_vertices)
+        nbox = len(self.layouts[0]["centres"])
+        return verts[:, n0:n0 + nbox].contiguous(), cnt[:, n0:n0 + nbox].contiguous()
+
+    def rrt_workspace_bytes(self, config=None):
+        """Bytes of workspace that ``rrt_plan`` needs with `config`: per env (max_nodes + 2) * 20 bytes, 520 KB at the reference's 26000."""
+        from ..planning import RRTConfig
+        cfg = (config or RRTConfig()).as_struct(self)
+        n = self.L.bp_rrt_workspace_bytes(C.byref(cfg), self.num_envs)
+        if n < 0:
+            raise _lib.BpError("bp_rrt_workspace_bytes refuses the config (step <= 0, max_nodes < 1, max_waypoints < 2, ...)")
+        return int(n)
+
+    def rrt_plan(self, starts=None, goals=None, walls=None, boxes=None, counts=None, streams=None, active=None, config=None, workspace=None, out=None):
+        """The reference's two-pass RRT, ``_densify`` and ``prune_by_distance`` for every env in one launch (bp_rrt_plan), no host synchronisation.
+        DESIGN.md "RRT" states the semantics.  All tensors are contiguous and on the env's device:
+
+        starts     float64 [E, 2] or None: info[:, :2]
+        goals      float64 [E, 2] or None: cfg.env.goal_x / goal_y for every env
+        walls      float64 [W, 4] or None: the handle's own walls
+        boxes      float64 [E, B, V, 2] with counts int32 [E, B], or both None: the box rows of ``world_polys()``.  Convex, 3 .. V vertices, either
+                   winding; a count of 0 skips the polygon
+        streams    int64 [E] or None: env_id_offset + arange(E).  A plan depends on the env's own inputs and its stream only
+        active     bool / uint8 [E] or None: envs with False get status RRT_SKIPPED and nothing else written
+        config     ``planning.RRTConfig`` or None (the reference's values; inflate_radius None: 2.25 * cfg.robot.min_r)
+        workspace  uint8 [>= rrt_workspace_bytes(config)] or None (allocated, and kept for the next call).  520 KB per env at the reference's max_nodes:
+                   a caller short of memory plans with a smaller env, or in groups through `active`
+        out        None or an earlier result to be overwritten
+
+        Returns ``planning.RRTPlan``: status int32 [E] (_lib.RRT_*), n_nodes and iterations int32 [E, 2] (per pass), paths float64
+        [E, max_waypoints, 2], lengths int32 [E].  Raises ValueError, before any launch, for a wrong dtype, device, shape or a non-contiguous tensor;
+        BpError for what the library refuses.  Touches no environment state."""
+        from ..planning import RRTConfig, RRTPlan
+        E, dev, fn = self.num_envs, self.device, "rrt_plan"
+        config = config or RRTConfig()
+        cfg = config.as_struct(self)
+        if starts is None:
+            starts = self.info[:, :2].contiguous()
+        if goals is None:
+            if getattr(self, "_rrt_goals", None) is None:
+                self._rrt_goals = torch.tensor([float(self.cfg.env.goal_x), float(self.cfg.env.goal_y)], dtype=torch.float64).to(dev)[None, :].expand(E, 2).contiguous()
+            goals = self._rrt_goals
+        if walls is None:
+            if getattr(self, "_rrt_walls", None) is None:
+                self._rrt_walls = torch.tensor(self.walls, dtype=torch.float64).reshape(-1, 4).to(dev)
+            walls = self._rrt_walls
+        if (boxes is None) != (counts is None):
+            raise ValueError("rrt_plan: boxes and counts go together")
+        if boxes is None:
+            boxes, counts = self.box_polys()
+        if streams is None:
+            streams = self.env_id_offset + torch.arange(E, dtype=torch.int64, device=dev)
+        self._need(fn, starts, "starts", torch.float64, (E, 2))
+        self._need(fn, goals, "goals", torch.float64, (E, 2))
+        self._need(fn, walls, "walls", torch.float64, (None, 4))
+        self._need(fn, boxes, "boxes", torch.float64, (E, None, None, 2))
+        self._need(fn, counts, "counts", torch.int32, (E, boxes.shape[1]))
+        self._need(fn, streams, "streams", torch.int64, (E,))
+        if active is not None:
+            self._need(fn, active, "active", (torch.bool, torch.uint8), (E,))
+        P = int(cfg.max_waypoints)
+        if out is not None:
+            self._need(fn, out.status, "out.status", torch.int32, (E,))
+            self._need(fn, out.n_nodes, "out.n_nodes", torch.int32, (E, 2))
+            self._need(fn, out.iterations, "out.iterations", torch.int32, (E, 2))
+            self._need(fn, out.paths, "out.paths", torch.float64, (E, P, 2))
+            self._need(fn, out.lengths, "out.lengths", torch.int32, (E,))
+        else:
+            out = RRTPlan(torch.zeros(E, dtype=torch.int32, device=dev), torch.zeros((E, 2), dtype=torch.int32, device=dev),
+                          torch.zeros((E, 2), dtype=torch.int32, device=dev), torch.zeros((E, max(P, 0), 2), dtype=torch.float64, device=dev),
+                          torch.zeros(E, dtype=torch.int32, device=dev))
+        if workspace is None:
+            need = self.L.bp_rrt_workspace_bytes(C.byref(cfg), E)
+            workspace = getattr(self, "_rrt_ws", None)
+            if need > 0 and (workspace is None or workspace.numel() < need):
+                workspace = self._rrt_ws = torch.empty(int(need), dtype=torch.uint8, device=dev)
+            elif workspace is None:
+                workspace = torch.empty(16, dtype=torch.uint8, device=dev)     # a config that the library is about to refuse
+        self._need(fn, workspace, "workspace", torch.uint8, (None,))
+        _lib.check(self.L, self.h, self.L.bp_rrt_plan(
+            self.h, C.byref(cfg), _ptr(starts), _ptr(goals), _ptr(walls) if walls.shape[0] else None, int(walls.shape[0]),
+            _ptr(boxes) if boxes.numel() else None, _ptr(counts) if boxes.numel() else None, int(boxes.shape[1]) if boxes.numel() else 0,
+            int(boxes.shape[2]), _ptr(streams), _ptr(active), _ptr(workspace), int(workspace.numel()), _ptr(out.status), _ptr(out.n_nodes),
+            _ptr(out.iterations), _ptr(out.paths), _ptr(out.lengths), self._stream()), "bp_rrt_plan")
+        return out
+
+    def track_waypoints(self, paths, lengths=None, poses=None, active=None, Lfc=0.5, dt=0.8, action_scale=None, out=None):
+        """The reference's maze controller -- ``DP.ideal_control`` of a fresh ``DP`` on the path, as ``PlanningBasedPolicy.act`` calls it -- for every env
+        in one launch (bp_track_waypoints), no host synchronisation.  paths float64 [E, P, 2]; lengths int32 [E] or None (all P); poses float64 [E, 3]
+        or None (info[:, :3]); active bool / uint8 [E] or None; Lfc and dt as in rrt_config.yaml; action_scale None: max_yaw_rate_step; out None or
+        (actions, diag) to be overwritten.  Returns (actions float64 [E] -- what ``step`` takes --, diag int32 [E, 2] = nearest and target index).  An
+        env that is not active, has a length below 1, or a non-finite pose or counted waypoint gets NaN and (-1, -1)."""
+        E, dev, fn = self.num_envs, self.device, "track_waypoints"
+        self._need(fn, paths, "paths", torch.float64, (E, None, 2))
+        if lengths is not None:
+            self._need(fn, lengths, "lengths", torch.int32, (E,))
+        if poses is None:
+            poses = self.info[:, :3].contiguous()
+        self._need(fn, poses, "poses", torch.float64, (E, 3))
+        if active is not None:
+            self._need(fn, active, "active", (torch.bool, torch.uint8), (E,))
+        if out is not None:
+            actions, diag = out
+            self._need(fn, actions, "out[0]", torch.float64, (E,))
+            self._need(fn, diag, "out[1]", torch.int32, (E, 2))
+        else:
+            actions, diag = torch.zeros(E, dtype=torch.float64, device=dev), torch.zeros((E, 2), dtype=torch.int32, device=dev)
+        cfg = _lib.BpTrackWpConfig(P=int(paths.shape[1]), pad_=0, Lfc=float(Lfc), dt=float(dt),
+                                   action_scale=float(self.max_yaw_rate_step if action_scale is None else action_scale))
+        _lib.check(self.L, self.h, self.L.bp_track_waypoints(self.h, C.byref(cfg), _ptr(paths), _ptr(lengths), _ptr(poses), _ptr(active), _ptr(actions),
+                                                             _ptr(diag), self._stream()), "bp_track_waypoints")
+        return actions, diag
+
 
 class MazeNAMO(Env):
     """Reference-shaped single environment (E = 1): reset()/step() returns and info keys of maze_NAMO_env.py:325-485."""

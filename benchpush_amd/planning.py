@@ -7,13 +7,15 @@ the sampled path of a search result (``lattice_full_paths``, ``AStar.build_path`
 ``LatticePlanner.plan``.  For ``BatchedShipIceEnv.track_paths``: the controller's tunables and integrators (``TrackerConfig``, ``TrackerState``) and the
 reference's ``straight_planner`` for a batch (``straight_paths``).
 """
+import collections
+
 import numpy as np
 import torch
 
 from . import dubins as _dubins
 
 __all__ = ["ship_footprint", "arc_paths", "replan_mask", "LATTICE_SHIP_VERTICES", "LatticePrimitives", "ship_halves", "lattice_max_val",
-           "lattice_swath_masks", "lattice_full_paths", "BatchedLatticePlanner", "TrackerConfig", "TrackerState", "straight_paths"]
+           "lattice_swath_masks", "lattice_full_paths", "BatchedLatticePlanner", "TrackerConfig", "TrackerState", "straight_paths", "RRTConfig", "RRTPlan"]
 
 # ship.vertices of the reference's lattice planner configuration (17 vertices, some collinear); with padding 0.25 and scale 5 it is the planner's footprint
 LATTICE_SHIP_VERTICES = [[1., -0.], [0.9, 0.10], [0.5, 0.25], [0.25, 0.25], [0, 0.25], [-0.25, 0.25], [-0.5, 0.25], [-0.75, 0.25], [-1., 0.25],
@@ -330,6 +332,32 @@ class BatchedLatticePlanner:
         bearing = torch.atan2(tgt[:, 1] - pose[:, 1], tgt[:, 0] - pose[:, 0])
         err = torch.remainder(bearing - pose[:, 2] + torch.pi, 2 * torch.pi) - torch.pi
         return torch.where(self.lengths > 0, (2.0 * err).clamp(-1.0, 1.0), torch.zeros_like(err))
+
+
+class RRTPlan(collections.namedtuple("RRTPlan", "status n_nodes iterations paths lengths")):
+    """What ``BatchedMazeEnv.rrt_plan`` returns, device tensors: status int32 [E] (``_lib.RRT_*``), n_nodes and iterations int32 [E, 2] (one column
+    per pass), paths float64 [E, max_waypoints, 2] (the pruned waypoints) and lengths int32 [E]."""
+    __slots__ = ()
+
+
+class RRTConfig:
+    """The reference's RRT as data: rrt_config.yaml (step, goal_radius, goal_bias, max_nodes, densify_ds, seed), the ``min_dist`` that its policy
+    prunes with, and this port's own: inflate_radius (None: 2.25 * cfg.robot.min_r, the reference's 1.5 * (1.5 * min_r)), max_waypoints (rows of the
+    returned paths) and passes (2; 1: boxes always block).  Lfc and dt are the controller's (``track_waypoints``)."""
+    FIELDS = ("step", "goal_radius", "goal_bias", "densify_ds", "prune_min_dist")
+
+    def __init__(self, step=0.05, goal_radius=0.01, goal_bias=0.01, max_nodes=26000, densify_ds=0.08, prune_min_dist=0.3, inflate_radius=None, seed=42,
+                 max_waypoints=256, passes=2, Lfc=0.5, dt=0.8):
+        for k in self.FIELDS + ("Lfc", "dt"):
+            setattr(self, k, float(locals()[k]))
+        self.inflate_radius = None if inflate_radius is None else float(inflate_radius)
+        self.max_nodes, self.seed, self.max_waypoints, self.passes = int(max_nodes), int(seed), int(max_waypoints), int(passes)
+
+    def as_struct(self, env=None):
+        from . import _lib
+        r = self.inflate_radius if self.inflate_radius is not None else 1.5 * (1.5 * float(env.cfg.robot.min_r))   # policy.py, rrt.py: two factors of 1.5
+        return _lib.BpRrtConfig(inflate_radius=r, seed=self.seed & 0xFFFFFFFFFFFFFFFF, max_nodes=self.max_nodes, max_waypoints=self.max_waypoints,
+                                passes=self.passes, pad_=0, **{k: getattr(self, k) for k in self.FIELDS})
 
 
 class TrackerConfig:

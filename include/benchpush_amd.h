@@ -537,6 +537,73 @@ int32_t bp_sizeof_track_config(void);
 int bp_track_path(bp_handle *h, const bp_track_config *cfg, const double *paths, int64_t path_stride, const int32_t *lengths, const double *poses,
                   const uint8_t *active, double *state, double *actions, double *ct_err, int32_t *diag, void *stream);
 
+/* ---- batched RRT and the waypoint controller (maze handles) ----
+ * bp_rrt_plan: the reference's two-pass RRT (baselines/maze_NAMO/planning_based/RRT/rrt.py: RRTPlanner.plan, _run_rrt) followed by _densify and the
+ * policy's prune_by_distance, for every env in one launch, one wavefront per env (DESIGN.md "RRT" states the semantics and where they deviate from
+ * the reference; tests/rrt_ref.py restates them and the kernel is held to == against it).  Device memory, contiguous:
+ *   starts, goals  double [E][2]
+ *   walls          double [n_walls][4] = (ax, ay, bx, by), shared by all envs; n_walls <= BP_RRT_MAX_WALLS (may be 0, then walls may be NULL)
+ *   boxes          double [E][n_boxes][n_verts][2] with counts int32 [E][n_boxes]: convex polygons of 3 .. n_verts vertices, either winding; a count of
+ *                  0 skips the polygon; n_verts <= BP_MAXV and n_boxes * n_verts <= BP_RRT_MAX_BOX_VERTS (n_boxes may be 0, then both may be NULL)
+ *   streams        int64 [E]: the env's RNG stream.  A plan is a function of the config, the env's own inputs and its stream only -- not of E or of
+ *                  the env's place in the batch.  Sample j of iteration k of pass p is bp_rrt_uniform(seed, stream, p, k, j).
+ *   active         uint8 [E] or NULL (all)
+ *   workspace      bp_rrt_workspace_bytes(cfg, E) bytes, 16-byte aligned: per env (max_nodes + 2) nodes as (x, y) doubles, then (max_nodes + 2)
+ *                  int32 parents, rounded up to 16 bytes -- 520 KB per env at the reference's max_nodes of 26000, 2.1 GB for 4096 envs.  Inactive
+ *                  envs still own their slice; a caller short of memory plans a group of envs per call through `active` with a handle of that size.
+ *                  After the call an env's slice holds the tree of the last pass it ran (nodes 0 .. n_nodes - 1 and their parents, -1 at node 0).
+ *   status         int32 [E], BP_RRT_*
+ *   n_nodes, iterations  int32 [E][2]: per pass, the tree's size (the goal node included when found) and the loop iterations used; 0 for a pass not run
+ *   paths          double [E][max_waypoints][2] and lengths int32 [E]: the pruned waypoints; rows from `lengths` on are not written
+ * Status: BP_RRT_FOUND (pass 0, boxes block) and BP_RRT_FOUND_IGNORING_BOXES (pass 1): the pruned waypoints.  BP_RRT_FALLBACK (every pass used up
+ * max_nodes) and BP_RRT_BLOCKED (start or goal within inflate_radius of a wall; no search): the path [start, goal], as the reference returns.
+ * BP_RRT_CAP (more than max_waypoints waypoints): length 0, the first max_waypoints waypoints are in `paths`.  BP_RRT_BAD_INPUT (a non-finite start,
+ * goal, wall or counted vertex, or a count outside 0, 3 .. n_verts): length 0.  BP_RRT_SKIPPED (active == 0): nothing but the status is written.
+ * BP_EINVAL, with nothing launched or written, for a NULL required pointer, a handle that is not a maze, step <= 0, goal_radius < 0, max_nodes < 1,
+ * max_waypoints < 2, passes outside 1 .. 2, a non-finite or negative config value, more than 2^22 dense points in all
+ * ((max_nodes + 2) * max(1, max(step, goal_radius) / max(1e-3, densify_ds)): what bounds _densify), sizes over the caps above, or a workspace that is short or not 16-byte aligned; BP_ESTATE before
+ * load and reset.  Reads the handle's device and size only.  Enqueued on `stream`; a function of its inputs bit for bit.
+ * BP_RRT_LDS_NODES in the environment (read at every call; a multiple of 64 up to 2048, 0: none) is how many of the tree's first nodes the nearest
+ * search keeps in LDS; it changes the time of a launch and nothing else (profiles/rrt/README.md). */
+#define BP_RRT_MAX_WALLS 128
+#define BP_RRT_MAX_BOX_VERTS 1280
+enum { BP_RRT_FOUND = 0, BP_RRT_FOUND_IGNORING_BOXES = 1, BP_RRT_FALLBACK = 2, BP_RRT_BLOCKED = 3, BP_RRT_CAP = 4, BP_RRT_BAD_INPUT = 5, BP_RRT_SKIPPED = 6 };
+typedef struct bp_rrt_config {
+    double step, goal_radius, goal_bias;   /* rrt_config.yaml: 0.05, 0.01, 0.01 */
+    double densify_ds, prune_min_dist;     /* 0.08; policy.py's prune_by_distance(min_dist=0.3) */
+    double inflate_radius;                 /* walls block within this distance: the reference's 1.5 * (1.5 * robot.min_r) */
+    uint64_t seed;                         /* 42 */
+    int32_t max_nodes;                     /* iterations per pass: 26000 */
+    int32_t max_waypoints;                 /* rows of `paths` per env */
+    int32_t passes;                        /* 2; 1: boxes always block, no second pass */
+    int32_t pad_;
+} bp_rrt_config;
+int32_t bp_sizeof_rrt_config(void);
+int64_t bp_rrt_workspace_bytes(const bp_rrt_config *cfg, int32_t num_envs);   /* BP_EINVAL (negative) for a config that bp_rrt_plan refuses */
+double bp_rrt_uniform(uint64_t seed, int64_t stream, int32_t pass, int32_t iteration, int32_t draw);   /* host function; the kernel's draws */
+int bp_rrt_plan(bp_handle *h, const bp_rrt_config *cfg, const double *starts, const double *goals, const double *walls, int32_t n_walls,
+                const double *boxes, const int32_t *counts, int32_t n_boxes, int32_t n_verts, const int64_t *streams, const uint8_t *active,
+                void *workspace, int64_t workspace_bytes, int32_t *status, int32_t *n_nodes, int32_t *iterations, double *paths, int32_t *lengths,
+                void *stream);
+
+/* bp_track_waypoints: what the reference's maze policy does with the path at every step (policy.py: act builds a fresh DP and calls
+ * DP.ideal_control, common/controller/dp.py), so the controller keeps no state: the nearest waypoint (first minimum), advanced while it is within Lfc
+ * and a next one exists; theta_e = atan2(sin(e), cos(e)), e = atan2(yd - y, xd - x) - yaw; action = theta_e / dt / action_scale.
+ *   paths double [E][P][2], lengths int32 [E] or NULL (all P), poses double [E][3] = (x, y, yaw), active uint8 [E] or NULL,
+ *   actions double [E], diag int32 [E][2] = (nearest index, target index)
+ * An env with active == 0, a length below 1, or a non-finite pose or counted waypoint gets a NaN action and diag (-1, -1).  BP_EINVAL, with nothing
+ * launched, for a NULL required pointer, P <= 0, Lfc that is not finite, dt or action_scale that is not positive and finite, or a handle that is not
+ * a maze; BP_ESTATE before load and reset. */
+typedef struct bp_track_wp_config {
+    int32_t P;                /* waypoints per path */
+    int32_t pad_;
+    double Lfc, dt;           /* rrt_config.yaml controller: look-ahead 0.5, dt 0.8 */
+    double action_scale;      /* the env's max_yaw_rate_step */
+} bp_track_wp_config;
+int32_t bp_sizeof_track_wp_config(void);
+int bp_track_waypoints(bp_handle *h, const bp_track_wp_config *cfg, const double *paths, const int32_t *lengths, const double *poses,
+                       const uint8_t *active, double *actions, int32_t *diag, void *stream);
+
 const char *bp_last_error(const bp_handle *h);
 int32_t bp_abi_version(void);
 int32_t bp_sizeof_config(void);   /* sizeof(bp_config), so a binding can verify its struct layout */
