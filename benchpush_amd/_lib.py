@@ -32,7 +32,11 @@ EXPORTS = ["bp_abi_version", "bp_create", "bp_destroy", "bp_load_scenarios", "bp
            "bp_sizeof_swath_config", "bp_swath_cost",
            "bp_sizeof_lattice_config", "bp_lattice_workspace_bytes", "bp_lattice_search",
            "bp_sizeof_track_config", "bp_track_path",
-           "bp_sizeof_rrt_config", "bp_rrt_workspace_bytes", "bp_rrt_uniform", "bp_rrt_plan", "bp_sizeof_track_wp_config", "bp_track_waypoints"]
+           "bp_sizeof_rrt_config", "bp_rrt_workspace_bytes", "bp_rrt_uniform", "bp_rrt_plan", "bp_sizeof_track_wp_config", "bp_track_waypoints",
+           "bp_sizeof_gtsp_config", "bp_gtsp_workspace_bytes", "bp_gtsp_plan", "bp_gtsp_track"]
+GTSP_OK, GTSP_NOTHING_TO_PUSH, GTSP_SKIPPED, GTSP_CAP, GTSP_INVALID = range(5)
+GTSP_STATUS_MASK, GTSP_FLAG_VANISHED, GTSP_FLAG_DEGENERATE = 0xFF, 0x100, 0x200   # status = code | flags
+GTSP_MAX_BOXES, GTSP_MAX_GOALS, GTSP_MAX_SLOTS = 12, 8, 64
 RRT_FOUND, RRT_FOUND_IGNORING_BOXES, RRT_FALLBACK, RRT_BLOCKED, RRT_CAP, RRT_BAD_INPUT, RRT_SKIPPED = range(7)
 RRT_MAX_WALLS, RRT_MAX_BOX_VERTS = 128, 1280   # bp_rrt_plan: walls, and box slots times vertices per slot, at most
 TRACK_NONE, TRACK_GENTLE, TRACK_PID, TRACK_NEAR = 0, 1, 2, 3
@@ -73,6 +77,11 @@ class BpRrtConfig(C.Structure):
 
 class BpTrackWpConfig(C.Structure):
     _fields_ = [("P", C.c_int32), ("pad_", C.c_int32), ("Lfc", C.c_double), ("dt", C.c_double), ("action_scale", C.c_double)]
+
+
+class BpGtspConfig(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("shrink", "extend", "lin_vel", "ang_vel", "Lfc", "dt", "target_speed", "switch_dist", "v_scale", "w_scale")] + [
+        ("round_decimals", C.c_int32), ("max_boxes", C.c_int32), ("num_goals", C.c_int32), ("pad_", C.c_int32)]
 
 
 class BpConfig(C.Structure):
@@ -250,6 +259,14 @@ def load():
         L.bp_rrt_uniform.restype = C.c_double
         L.bp_rrt_plan.argtypes = [vp, C.POINTER(BpRrtConfig), vp, vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_int64] + [vp] * 6
         L.bp_track_waypoints.argtypes = [vp, C.POINTER(BpTrackWpConfig)] + [vp] * 7
+    if hasattr(L, "bp_gtsp_plan"):   # the GTSP push planner and its controller (absent from older builds loaded for same-box comparisons)
+        L.bp_sizeof_gtsp_config.restype = C.c_int32
+        if L.bp_sizeof_gtsp_config() != C.sizeof(BpGtspConfig):
+            raise BpError("bp_gtsp_config layout mismatch between _lib.BpGtspConfig and the library")
+        L.bp_gtsp_workspace_bytes.argtypes = [C.POINTER(BpGtspConfig), C.c_int32]
+        L.bp_gtsp_workspace_bytes.restype = C.c_int64
+        L.bp_gtsp_plan.argtypes = [vp, C.POINTER(BpGtspConfig), vp, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_int64] + [vp] * 10
+        L.bp_gtsp_track.argtypes = [vp, C.POINTER(BpGtspConfig)] + [vp] * 9
     _lib = L
     return L
 

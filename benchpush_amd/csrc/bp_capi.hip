@@ -25,6 +25,7 @@
 #include "bp_lattice.hpp"
 #include "bp_track.hpp"
 #include "bp_rrt.hpp"
+#include "bp_gtsp.hpp"
 
 struct bp_handle {
     bp_config cfg;
@@ -1470,6 +1471,77 @@ int bp_track_waypoints(bp_handle *h, const bp_track_wp_config *cfg, const double
     TrackWpArgs A;
     A.c = *cfg; A.paths = paths; A.lengths = lengths; A.poses = poses; A.active = active; A.actions = actions; A.diag = diag;
     hipLaunchKernelGGL(k_track_waypoints, dim3((unsigned)h->num_envs), dim3(64), 0, (hipStream_t)stream, A);
+    HIPCHK(h, hipGetLastError());
+    return BP_OK;
+}
+// ---- the GTSP push planner and its controller ----
+int32_t bp_sizeof_gtsp_config(void) { return (int32_t)sizeof(bp_gtsp_config); }
+static const char *gtsp_config_error(const bp_gtsp_config *c)
+{
+    const double v[8] = {c->shrink, c->extend, c->lin_vel, c->ang_vel, c->Lfc, c->target_speed, c->switch_dist, 0.0};
+    for (double x : v) if (!std::isfinite(x) || x < 0.0) return "bp_gtsp: a config value is negative or not finite";
+    if (!(c->dt > 0.0) || !std::isfinite(c->dt) || !(c->v_scale > 0.0) || !std::isfinite(c->v_scale) || !(c->w_scale > 0.0) || !std::isfinite(c->w_scale))
+        return "bp_gtsp: dt, v_scale and w_scale must be positive and finite";
+    if (c->max_boxes < 1 || c->max_boxes > BP_GTSP_MAX_BOXES) return "bp_gtsp: max_boxes outside 1 .. BP_GTSP_MAX_BOXES";
+    if (c->num_goals < 1 || c->num_goals > BP_GTSP_MAX_GOALS) return "bp_gtsp: num_goals outside 1 .. BP_GTSP_MAX_GOALS";
+    if (c->round_decimals < 0 || c->round_decimals > 15) return "bp_gtsp: round_decimals outside 0 .. 15";
+    return nullptr;
+}
+static long long gtsp_per_env(const bp_gtsp_config *c) { return (((1ll << c->max_boxes) * c->max_boxes * c->num_goals * 4) + 15) & ~15ll; }
+int64_t bp_gtsp_workspace_bytes(const bp_gtsp_config *cfg, int32_t num_envs)
+{
+    if (!cfg || num_envs <= 0 || gtsp_config_error(cfg)) return BP_EINVAL;
+    return (int64_t)(gtsp_per_env(cfg) * num_envs);
+}
+static bool gtsp_handle(const bp_handle *h) { return h->P.env_kind == BP_ENV_BOX && h->bdcfg.task == 1; }
+int bp_gtsp_plan(bp_handle *h, const bp_gtsp_config *cfg, const double *poses, const double *boxes, const int32_t *counts, int32_t n_boxes,
+                 int32_t n_verts, const double *goals, const uint8_t *active, void *workspace, int64_t workspace_bytes, int32_t *status,
+                 int32_t *n_push, int32_t *tour, int32_t *cost, double *paths, int32_t *lengths, int32_t *track_id, double *track_setpoint,
+                 int32_t *weights, void *stream)
+{
+    if (!h) return BP_EINVAL;
+    if (!cfg || !poses || !goals || !workspace || !status || !n_push || !tour || !cost || !paths || !lengths || !track_id || !track_setpoint)
+        return fail(h, BP_EINVAL, "bp_gtsp_plan: NULL required pointer");
+    if (!gtsp_handle(h)) return fail(h, BP_EINVAL, "bp_gtsp_plan: area-clearing handles only");
+    if (!h->loaded || !h->was_reset) return fail(h, BP_ESTATE, "bp_gtsp_plan before bp_bd_load/bp_reset");
+    if (const char *e = gtsp_config_error(cfg)) return fail(h, BP_EINVAL, e);
+    if (n_boxes < 0 || n_boxes > BP_GTSP_MAX_SLOTS || (n_boxes > 0 && (n_verts < 3 || n_verts > BP_MAXV || !boxes || !counts)))
+        return fail(h, BP_EINVAL, "bp_gtsp_plan: n_boxes above BP_GTSP_MAX_SLOTS or n_verts outside 3 .. BP_MAXV");
+    const bp_bd_config &bc = h->bdcfg;
+    if (bc.num_boundary_verts < 3 || bc.num_boundary_verts > 8) return fail(h, BP_EINVAL, "bp_gtsp_plan: the handle has no boundary polygon");
+    const long long per_env = gtsp_per_env(cfg);
+    if (workspace_bytes < per_env * (long long)h->num_envs || (((uintptr_t)workspace) & 15u))
+        return fail(h, BP_EINVAL, "bp_gtsp_plan: workspace smaller than bp_gtsp_workspace_bytes or not 16-byte aligned");
+    BP_DEVICE(h);
+    GtspArgs A;
+    A.c = *cfg;
+    A.round_scale = 1.0;
+    for (int i = 0; i < cfg->round_decimals; i++) A.round_scale *= 10.0;       // exact up to 10^22
+    A.B = n_boxes; A.V = n_boxes > 0 ? n_verts : 0; A.G = cfg->num_goals; A.nb = bc.num_boundary_verts;
+    A.n_max = cfg->max_boxes; A.N_max = cfg->max_boxes * cfg->num_goals + 1; A.ws_per_env = per_env;
+    for (int i = 0; i < 8; i++) { A.boundary[i][0] = bc.boundary[i][0]; A.boundary[i][1] = bc.boundary[i][1]; }
+    A.poses = poses; A.boxes = boxes; A.goals = goals; A.counts = counts; A.active = active; A.ws = (char *)workspace;
+    A.status = status; A.n_push = n_push; A.tour = tour; A.cost = cost; A.lengths = lengths; A.track_id = track_id; A.W = weights;
+    A.paths = paths; A.track_sp = track_setpoint;
+    const size_t lds = (((size_t)A.N_max * A.N_max + 3) / 4 + (size_t)A.n_max * A.G * 3 + 2 * (size_t)A.n_max + 1) * 16;   // 42.6 KB at the caps
+    hipLaunchKernelGGL(k_gtsp_plan, dim3((unsigned)h->num_envs), dim3(64), lds, (hipStream_t)stream, A);
+    HIPCHK(h, hipGetLastError());
+    return BP_OK;
+}
+int bp_gtsp_track(bp_handle *h, const bp_gtsp_config *cfg, const double *paths, const int32_t *lengths, const double *poses, const uint8_t *active,
+                  int32_t *track_id, double *track_setpoint, double *actions, int32_t *diag, void *stream)
+{
+    if (!h) return BP_EINVAL;
+    if (!cfg || !paths || !lengths || !poses || !track_id || !track_setpoint || !actions || !diag)
+        return fail(h, BP_EINVAL, "bp_gtsp_track: NULL required pointer");
+    if (!gtsp_handle(h)) return fail(h, BP_EINVAL, "bp_gtsp_track: area-clearing handles only");
+    if (!h->loaded || !h->was_reset) return fail(h, BP_ESTATE, "bp_gtsp_track before bp_bd_load/bp_reset");
+    if (const char *e = gtsp_config_error(cfg)) return fail(h, BP_EINVAL, e);
+    BP_DEVICE(h);
+    GtspTrackArgs A;
+    A.c = *cfg; A.P = 2 * cfg->max_boxes + 1; A.paths = paths; A.poses = poses; A.lengths = lengths; A.active = active;
+    A.track_id = track_id; A.diag = diag; A.track_sp = track_setpoint; A.actions = actions;
+    hipLaunchKernelGGL(k_gtsp_track, dim3((unsigned)h->num_envs), dim3(64), 0, (hipStream_t)stream, A);
     HIPCHK(h, hipGetLastError());
     return BP_OK;
 }

@@ -17,6 +17,7 @@ from ..area_clearing_scenario import area_clearing_params, area_clearing_physics
 from ..config import default_cfg, merge_user_cfg
 from ..gym_shim import Env, spaces
 from .box_delivery import BatchedBoxDeliveryEnv, low_dim_observation
+from .ship_ice import _ptr
 
 __all__ = ["BatchedAreaClearingEnv", "AreaClearingEnv", "AC_INFO_KEYS"]
 AC_INFO_KEYS = ["x", "y", "theta", "total_work", "collision_reward", "diff_reward", "box_completed_reward", "box_count", "ministeps",
@@ -77,6 +78,147 @@ class BatchedAreaClearingEnv(BatchedBoxDeliveryEnv):
         self.obs = torch.zeros((self.num_envs,) + self.obs_shape, dtype=torch.uint8, device=self.device)
         self.action_dim = 2 if self.cfg.agent.action_type == "velocity" else 1
         self._actions = torch.zeros(self.num_envs * self.action_dim, dtype=torch.float64, device=self.device)
+        self.target_speed = float(self.cfg.controller.target_speed)     # area_clearing.py:196-209: what a 'velocity' action is scaled by
+        self.max_yaw_rate_step = (np.pi / 2) / 15
+
+    # -- the planning baseline's device calls (DESIGN.md "GTSP") --------------------------------------------
+    def _need(self, fn, t, name, dtypes, shape):
+        dtypes = dtypes if isinstance(dtypes, tuple) else (dtypes,)
+        if not isinstance(t, torch.Tensor) or t.dtype not in dtypes or t.device != self.device or not t.is_contiguous():
+            raise ValueError("%s: %s must be a contiguous %s tensor on %s" % (fn, name, " / ".join(map(str, dtypes)), self.device))
+        if t.dim() != len(shape) or any(a is not None and a != b for a, b in zip(shape, t.shape)):
+            raise ValueError("%s: %s has shape %s, expected %s" % (fn, name, tuple(t.shape), list(shape)))
+
+    def push_box_polys(self):
+        """The box rows of ``world_polys()``: (verts [E, nbox, 20, 2] f64, counts [E, nbox] i32), contiguous."""
+        verts, cnt = self.world_polys()
+        return verts[:, 6:6 + self.nbox].contiguous(), cnt[:, 6:6 + self.nbox].contiguous()
+
+    def boundary_goals(self):
+        """``planning.boundary_goals`` of this handle's layout, computed once: (numpy [G, 2, 2], device tensor [G, 4])."""
+        if getattr(self, "_gtsp_goals", None) is None:
+            from ..planning import boundary_goals
+            lay = env_layout(self.cfg)
+            g = boundary_goals(lay.boundary, lay.walls if "walls" in lay else [])
+            self._gtsp_goals = (g, torch.from_numpy(np.ascontiguousarray(g.reshape(-1, 4))).to(self.device))
+        return self._gtsp_goals
+
+    def _gtsp_struct(self, config, goals=None):
+        from ..planning import GTSPConfig
+        config = config or GTSPConfig()
+        G = config.num_goals
+        if G is None:
+            G = int(goals.shape[0]) if goals is not None else len(self.boundary_goals()[0])
+        return config.as_struct(self, num_goals=G)
+
+    def gtsp_workspace_bytes(self, config=None):
+        """Bytes of workspace that ``gtsp_plan`` needs with `config`: per env 2^max_boxes * max_boxes * num_goals int32 (160 KB at 10 boxes, 4 goals)."""
+        cfg = self._gtsp_struct(config)
+        n = self.L.bp_gtsp_workspace_bytes(C.byref(cfg), self.num_envs)
+        if n < 0:
+            raise _lib.BpError("bp_gtsp_workspace_bytes refuses the config (max_boxes outside 1 .. 12, num_goals outside 1 .. 8, ...)")
+        return int(n)
+
+    def gtsp_plan(self, poses=None, boxes=None, counts=None, goals=None, active=None, config=None, workspace=None, out=None, return_weights=False):
+        """The reference's GTSP push plan for every env in one launch (bp_gtsp_plan), solved exactly, no host synchronisation.  DESIGN.md "GTSP"
+        states the semantics.  All tensors are contiguous and on the env's device:
+
+        poses      float64 [E, 3] or None: info[:, :3]
+        boxes      float64 [E, B, V, 2] with counts int32 [E, B], or both None: ``push_box_polys()``.  Convex, 3 .. V vertices, either winding; a count
+                   of 0 skips the slot.  A box is pushed iff it intersects the handle's clearance boundary
+        goals      float64 [G, 4] = (ax, ay, bx, by) or None: ``boundary_goals()`` of the handle's layout
+        active     bool / uint8 [E] or None: envs with False get status GTSP_SKIPPED and nothing else written
+        config     ``planning.GTSPConfig`` or None (the reference's values)
+        workspace  uint8 [>= gtsp_workspace_bytes(config)] or None (allocated, and kept for the next call)
+        out        None or an earlier result to be overwritten
+        return_weights  also the integer weight matrix, int32 [E, N_max, N_max] with N_max = max_boxes * G + 1
+
+        Returns ``planning.GTSPPlan``.  Raises ValueError, before any launch, for a wrong dtype, device, shape or a non-contiguous tensor; BpError for
+        what the library refuses.  Touches no environment state."""
+        from ..planning import GTSPPlan
+        E, dev, fn = self.num_envs, self.device, "gtsp_plan"
+        if poses is None:
+            poses = self.info[:, :3].contiguous()
+        if (boxes is None) != (counts is None):
+            raise ValueError("gtsp_plan: boxes and counts go together")
+        if boxes is None:
+            boxes, counts = self.push_box_polys()
+        if goals is None:
+            goals = self.boundary_goals()[1]
+        self._need(fn, goals, "goals", torch.float64, (None, 4))
+        cfg = self._gtsp_struct(config, goals)
+        if goals.shape[0] != cfg.num_goals:
+            raise ValueError("gtsp_plan: goals has %d rows, config.num_goals is %d" % (goals.shape[0], cfg.num_goals))
+        self._need(fn, poses, "poses", torch.float64, (E, 3))
+        self._need(fn, boxes, "boxes", torch.float64, (E, None, None, 2))
+        self._need(fn, counts, "counts", torch.int32, (E, boxes.shape[1]))
+        if active is not None:
+            self._need(fn, active, "active", (torch.bool, torch.uint8), (E,))
+        nm, G = max(int(cfg.max_boxes), 0), int(cfg.num_goals)
+        Nm = nm * G + 1
+        if out is not None:
+            self._need(fn, out.status, "out.status", torch.int32, (E,))
+            self._need(fn, out.n_push, "out.n_push", torch.int32, (E,))
+            self._need(fn, out.tour, "out.tour", torch.int32, (E, nm))
+            self._need(fn, out.cost, "out.cost", torch.int32, (E,))
+            self._need(fn, out.paths, "out.paths", torch.float64, (E, 2 * nm + 1, 3))
+            self._need(fn, out.lengths, "out.lengths", torch.int32, (E,))
+            self._need(fn, out.track_id, "out.track_id", torch.int32, (E,))
+            self._need(fn, out.track_setpoint, "out.track_setpoint", torch.float64, (E, 2))
+            if return_weights:
+                if out.weights is None:
+                    raise ValueError("gtsp_plan: return_weights needs out.weights")
+                self._need(fn, out.weights, "out.weights", torch.int32, (E, Nm, Nm))
+        else:
+            z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)   # noqa: E731
+            big = nm > _lib.GTSP_MAX_BOXES or G > _lib.GTSP_MAX_GOALS        # a config that the library is about to refuse: allocate nothing large
+            out = GTSPPlan(z(E, torch.int32), z(E, torch.int32), z((E, nm), torch.int32), z(E, torch.int32), z((E, 2 * nm + 1, 3), torch.float64),
+                           z(E, torch.int32), z(E, torch.int32), z((E, 2), torch.float64),
+                           z((E, Nm, Nm), torch.int32) if return_weights and not big else None)
+        if workspace is None:
+            need = self.L.bp_gtsp_workspace_bytes(C.byref(cfg), E)
+            workspace = getattr(self, "_gtsp_ws", None)
+            if need > 0 and (workspace is None or workspace.numel() < need):
+                workspace = self._gtsp_ws = torch.empty(int(need), dtype=torch.uint8, device=dev)
+            elif workspace is None:
+                workspace = torch.empty(16, dtype=torch.uint8, device=dev)     # a config that the library is about to refuse
+        self._need(fn, workspace, "workspace", torch.uint8, (None,))
+        _lib.check(self.L, self.h, self.L.bp_gtsp_plan(
+            self.h, C.byref(cfg), _ptr(poses), _ptr(boxes) if boxes.numel() else None, _ptr(counts) if boxes.numel() else None,
+            int(boxes.shape[1]) if boxes.numel() else 0, int(boxes.shape[2]), _ptr(goals), _ptr(active), _ptr(workspace), int(workspace.numel()),
+            _ptr(out.status), _ptr(out.n_push), _ptr(out.tour), _ptr(out.cost), _ptr(out.paths), _ptr(out.lengths), _ptr(out.track_id),
+            _ptr(out.track_setpoint), _ptr(out.weights) if return_weights else None, self._stream()), "bp_gtsp_plan")
+        return out
+
+    def track_pushes(self, plan, tracker, poses=None, active=None, config=None, out=None):
+        """One call of the reference's ``PlanningBasedPolicy.act`` after planning, for every env in one launch (bp_gtsp_track), no host
+        synchronisation.  plan: a ``GTSPPlan`` (its paths and lengths are read); tracker: a ``planning.GTSPTrackerState``, updated in place; poses
+        float64 [E, 3] or None (info[:, :3]); active bool / uint8 [E] or None; config: the ``GTSPConfig`` the plan was made with (None: the
+        reference's values); out None or (actions, diag) to be overwritten.  Returns (actions float64 [E, 2] -- what ``step`` takes with
+        action_type 'velocity' --, diag int32 [E] = current_point_id).  An env that is not active, has a length below 2, or a non-finite pose or
+        counted waypoint gets NaN and -1, and its state is left as it is."""
+        E, dev, fn = self.num_envs, self.device, "track_pushes"
+        cfg = self._gtsp_struct(config)
+        P = 2 * int(cfg.max_boxes) + 1
+        self._need(fn, plan.paths, "plan.paths", torch.float64, (E, P, 3))
+        self._need(fn, plan.lengths, "plan.lengths", torch.int32, (E,))
+        self._need(fn, tracker.ids, "tracker.ids", torch.int32, (E,))
+        self._need(fn, tracker.setpoint, "tracker.setpoint", torch.float64, (E, 2))
+        if poses is None:
+            poses = self.info[:, :3].contiguous()
+        self._need(fn, poses, "poses", torch.float64, (E, 3))
+        if active is not None:
+            self._need(fn, active, "active", (torch.bool, torch.uint8), (E,))
+        if out is not None:
+            actions, diag = out
+            self._need(fn, actions, "out[0]", torch.float64, (E, 2))
+            self._need(fn, diag, "out[1]", torch.int32, (E,))
+        else:
+            actions, diag = torch.zeros((E, 2), dtype=torch.float64, device=dev), torch.zeros(E, dtype=torch.int32, device=dev)
+        _lib.check(self.L, self.h, self.L.bp_gtsp_track(self.h, C.byref(cfg), _ptr(plan.paths), _ptr(plan.lengths), _ptr(poses), _ptr(active),
+                                                        _ptr(tracker.ids), _ptr(tracker.setpoint), _ptr(actions), _ptr(diag), self._stream()),
+                   "bp_gtsp_track")
+        return actions, diag
 
 
 class AreaClearingEnv(Env):

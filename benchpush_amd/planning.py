@@ -5,7 +5,9 @@ form, the replanning comparison of ``Path.update`` (common/utils/utils.py:58-89)
 takes and gives: the primitive tables (``LatticePrimitives``, common/primitives.py), the swath masks (``lattice_swath_masks``, common/swath.py:15-88) and
 the sampled path of a search result (``lattice_full_paths``, ``AStar.build_path``).  ``BatchedLatticePlanner`` chains them into the planning round of
 ``LatticePlanner.plan``.  For ``BatchedShipIceEnv.track_paths``: the controller's tunables and integrators (``TrackerConfig``, ``TrackerState``) and the
-reference's ``straight_planner`` for a batch (``straight_paths``).
+reference's ``straight_planner`` for a batch (``straight_paths``).  For ``BatchedMazeEnv.rrt_plan``: ``RRTConfig``, ``RRTPlan``.  For
+``BatchedAreaClearingEnv.gtsp_plan`` / ``track_pushes``: ``GTSPConfig``, ``GTSPPlan``, ``GTSPTrackerState`` and the boundary goal segments of the
+reference's area-clearing policy (``boundary_goals``).
 """
 import collections
 
@@ -15,7 +17,8 @@ import torch
 from . import dubins as _dubins
 
 __all__ = ["ship_footprint", "arc_paths", "replan_mask", "LATTICE_SHIP_VERTICES", "LatticePrimitives", "ship_halves", "lattice_max_val",
-           "lattice_swath_masks", "lattice_full_paths", "BatchedLatticePlanner", "TrackerConfig", "TrackerState", "straight_paths", "RRTConfig", "RRTPlan"]
+           "lattice_swath_masks", "lattice_full_paths", "BatchedLatticePlanner", "TrackerConfig", "TrackerState", "straight_paths", "RRTConfig", "RRTPlan",
+           "GTSPConfig", "GTSPPlan", "GTSPTrackerState", "boundary_goals"]
 
 # ship.vertices of the reference's lattice planner configuration (17 vertices, some collinear); with padding 0.25 and scale 5 it is the planner's footprint
 LATTICE_SHIP_VERTICES = [[1., -0.], [0.9, 0.10], [0.5, 0.25], [0.25, 0.25], [0, 0.25], [-0.25, 0.25], [-0.5, 0.25], [-0.75, 0.25], [-1., 0.25],
@@ -358,6 +361,143 @@ class RRTConfig:
         r = self.inflate_radius if self.inflate_radius is not None else 1.5 * (1.5 * float(env.cfg.robot.min_r))   # policy.py, rrt.py: two factors of 1.5
         return _lib.BpRrtConfig(inflate_radius=r, seed=self.seed & 0xFFFFFFFFFFFFFFFF, max_nodes=self.max_nodes, max_waypoints=self.max_waypoints,
                                 passes=self.passes, pad_=0, **{k: getattr(self, k) for k in self.FIELDS})
+
+
+class GTSPPlan(collections.namedtuple("GTSPPlan", "status n_push tour cost paths lengths track_id track_setpoint weights")):
+    """What ``BatchedAreaClearingEnv.gtsp_plan`` returns, device tensors: status int32 [E] (``_lib.GTSP_*`` in the low byte, ``GTSP_FLAG_*`` above),
+    n_push int32 [E], tour int32 [E, max_boxes] (node c * G + g: cluster c to goal g), cost int32 [E], paths float64 [E, 2 * max_boxes + 1, 3],
+    lengths int32 [E], the tracker's first state track_id int32 [E] / track_setpoint float64 [E, 2], and weights int32 [E, N_max, N_max] or None."""
+    __slots__ = ()
+
+    def tracker(self):
+        """A fresh ``GTSPTrackerState`` at the plan's first state (copies)."""
+        return GTSPTrackerState(ids=self.track_id.clone(), setpoint=self.track_setpoint.clone())
+
+
+class GTSPConfig:
+    """The reference's GTSP baseline as data: policy.py (the box is shrunk by 0.4, the push path extended by 2 behind the box and rounded to 7 decimals,
+    the controller switches waypoints within 0.4), transition_graph_lookup.py (cost = 0.5 * length + pi / 4 * angle) and gtsp_config.yaml's controller
+    (Lfc 0.5, dt 0.8, target_speed 0.2).  This port's own: max_boxes (boxes to push at most, <= 12: the DP table has 2^max_boxes rows) and num_goals
+    (None: as many as the env's boundary goals, <= 8).  v_scale / w_scale None: the env's target_speed and max_yaw_rate_step."""
+    FIELDS = ("shrink", "extend", "lin_vel", "ang_vel", "Lfc", "dt", "target_speed", "switch_dist")
+
+    def __init__(self, shrink=0.4, extend=2.0, lin_vel=0.5, ang_vel=np.pi / 4, round_decimals=7, max_boxes=10, num_goals=None, Lfc=0.5, dt=0.8,
+                 target_speed=0.2, switch_dist=0.4, v_scale=None, w_scale=None):
+        for k in self.FIELDS:
+            v = float(locals()[k])
+            if not (np.isfinite(v) and v >= 0.0):
+                raise ValueError("GTSPConfig: %s must be finite and not negative" % k)
+            setattr(self, k, v)
+        if not self.dt > 0.0:
+            raise ValueError("GTSPConfig: dt must be positive")
+        self.round_decimals, self.max_boxes = int(round_decimals), int(max_boxes)
+        self.num_goals = None if num_goals is None else int(num_goals)
+        if not 0 <= self.round_decimals <= 15:
+            raise ValueError("GTSPConfig: round_decimals must be 0 .. 15")
+        if self.max_boxes < 1 or (self.num_goals is not None and self.num_goals < 1):
+            raise ValueError("GTSPConfig: max_boxes and num_goals must be positive")    # the upper caps are the library's to refuse
+        self.v_scale = None if v_scale is None else float(v_scale)
+        self.w_scale = None if w_scale is None else float(w_scale)
+        for k in ("v_scale", "w_scale"):
+            v = getattr(self, k)
+            if v is not None and not (np.isfinite(v) and v > 0.0):
+                raise ValueError("GTSPConfig: %s must be positive and finite" % k)
+
+    def as_dict(self):
+        return dict({k: getattr(self, k) for k in self.FIELDS}, round_decimals=self.round_decimals, max_boxes=self.max_boxes, num_goals=self.num_goals)
+
+    def as_struct(self, env=None, num_goals=None):
+        from . import _lib
+        G = self.num_goals if self.num_goals is not None else num_goals
+        v = self.v_scale if self.v_scale is not None else float(env.target_speed)
+        w = self.w_scale if self.w_scale is not None else float(env.max_yaw_rate_step)
+        return _lib.BpGtspConfig(v_scale=v, w_scale=w, round_decimals=self.round_decimals, max_boxes=self.max_boxes, num_goals=int(G), pad_=0,
+                                 **{k: getattr(self, k) for k in self.FIELDS})
+
+
+class GTSPTrackerState:
+    """What the GTSP controller keeps between calls, on the device: ``ids`` int32 [E] (``current_point_id``) and ``setpoint`` float64 [E, 2]."""
+
+    def __init__(self, num_envs=None, device="cuda:0", ids=None, setpoint=None):
+        self.ids = torch.ones(int(num_envs), dtype=torch.int32, device=device) if ids is None else ids
+        self.setpoint = torch.zeros((self.ids.shape[0], 2), dtype=torch.float64, device=self.ids.device) if setpoint is None else setpoint
+
+    def take(self, plan, mask=None):
+        """The first state of `plan` for the envs of `mask` (bool / uint8 [E]; None: all).  No host synchronisation."""
+        if mask is None:
+            self.ids.copy_(plan.track_id)
+            self.setpoint.copy_(plan.track_setpoint)
+        else:
+            m = mask.to(device=self.ids.device, dtype=torch.bool)
+            self.ids.copy_(torch.where(m, plan.track_id, self.ids))
+            self.setpoint.copy_(torch.where(m[:, None], plan.track_setpoint, self.setpoint))
+        return self
+
+    def clone(self):
+        return GTSPTrackerState(ids=self.ids.clone(), setpoint=self.setpoint.clone())
+
+
+def boundary_goals(boundary, walls, buffer=0.1, min_len=0.1):
+    """``PlanningBasedPolicy._compute_boundary_goals`` (policy.py:88-117) in numpy: every edge of the boundary polygon minus the `buffer`-capsule of
+    every wall segment, pieces no longer than `min_len` dropped.  Returns float64 [G, 2, 2] in edge order, the pieces of an edge from its start.  The
+    capsule is exact (a stadium), where shapely's ``buffer`` is a polygon with 16 segments per quarter circle."""
+    bd = np.asarray(boundary, np.float64).reshape(-1, 2)
+    out = []
+    for i in range(len(bd)):
+        a, b = bd[i], bd[(i + 1) % len(bd)]
+        d = b - a
+        L = float(np.hypot(d[0], d[1]))
+        if L == 0.0:
+            continue
+        cut = []                                         # parameter intervals of the edge inside some capsule
+        for w in ([] if walls is None else walls):
+            w = np.asarray(w, np.float64).reshape(-1, 2)
+            for k in range(len(w) - 1):
+                iv = _capsule_interval(a, d, L, w[k], w[k + 1], float(buffer))
+                if iv is not None:
+                    cut.append(iv)
+        t0 = 0.0
+        for lo, hi in sorted(cut):
+            if lo > t0 and (lo - t0) * L > min_len:
+                out.append([a + t0 * d, a + lo * d])
+            t0 = max(t0, hi)
+        if t0 < 1.0 and (1.0 - t0) * L > min_len:
+            out.append([a + t0 * d, b])
+    return np.asarray(out, np.float64).reshape(-1, 2, 2)
+
+
+def _capsule_interval(a, d, L, p, q, r):
+    """The parameters t in [0, 1] of a + t * d whose distance to the segment (p, q) is below r: one interval (the distance is convex in t), or None."""
+    def dist(t):
+        x = a + t * d
+        e = q - p
+        l2 = float(e @ e)
+        s = 0.0 if l2 == 0.0 else min(1.0, max(0.0, float((x - p) @ e) / l2))
+        return float(np.hypot(*(x - (p + s * e))))
+    lo, hi = 0.0, 1.0                                    # ternary search for the minimum of a convex function, then bisection for the two crossings
+    for _ in range(200):
+        m1, m2 = lo + (hi - lo) / 3, hi - (hi - lo) / 3
+        if dist(m1) <= dist(m2):
+            hi = m2
+        else:
+            lo = m1
+    tm = (lo + hi) / 2
+    if not dist(tm) < r:
+        return None
+    ends = []
+    for end in (0.0, 1.0):
+        if dist(end) < r:
+            ends.append(end)
+            continue
+        inside, outside = tm, end
+        for _ in range(200):
+            mid = (inside + outside) / 2
+            if dist(mid) < r:
+                inside = mid
+            else:
+                outside = mid
+        ends.append(inside)
+    return ends[0], ends[1]
 
 
 class TrackerConfig:

@@ -604,6 +604,62 @@ int32_t bp_sizeof_track_wp_config(void);
 int bp_track_waypoints(bp_handle *h, const bp_track_wp_config *cfg, const double *paths, const int32_t *lengths, const double *poses,
                        const uint8_t *active, double *actions, int32_t *diag, void *stream);
 
+/* ---- the GTSP push planner and its controller (area-clearing handles) ----
+ * bp_gtsp_plan: the reference's planning-based area-clearing baseline (baselines/area_clearing/planning_based/policy.py: plan_path;
+ * GTSPPlanner/transition_graph_lookup.py; create_instance.py) for every env in one launch, one wavefront per env, with an exact set DP in the place of
+ * the GLNS heuristic (DESIGN.md "GTSP" states the semantics and the deviations; tests/gtsp_ref.py restates them and the kernels are held to ==
+ * against it).  A box is pushed iff it intersects the handle's clearance boundary; cluster c is the c-th pushed box in slot order, node c * G + g
+ * pushes it to goal segment g, the robot is node n * G.  Device memory, contiguous:
+ *   poses          double [E][3] = (x, y, theta)
+ *   boxes          double [E][n_boxes][n_verts][2] with counts int32 [E][n_boxes]: convex polygons of 3 .. n_verts vertices, either winding; a count
+ *                  of 0 skips the slot; n_boxes <= BP_GTSP_MAX_SLOTS, n_verts <= BP_MAXV
+ *   goals          double [num_goals][4] = (ax, ay, bx, by), shared by all envs
+ *   active         uint8 [E] or NULL (all)
+ *   workspace      bp_gtsp_workspace_bytes(cfg, E) bytes, 16-byte aligned: per env the DP table int32 [2^max_boxes][max_boxes * num_goals]
+ *                  (160 KB at 10 boxes and 4 goals, 1.5 MB at the caps)
+ *   status         int32 [E]: BP_GTSP_* in the low byte, BP_GTSP_FLAG_* above it
+ *   n_push, cost, lengths  int32 [E]: pushed boxes, the tour's integer cost (robot -> nodes -> robot), rows of the path (2 * n_push + 1)
+ *   tour           int32 [E][max_boxes]: node indices in visiting order; entries from n_push on are not written
+ *   paths          double [E][2 * max_boxes + 1][3]: the pose, then per visited node (route start, heading) and (route end, heading)
+ *   track_id, track_setpoint  int32 [E], double [E][2]: the controller's first state (1, TargetCourse.init_setpoint on the path)
+ *   weights        int32 [E][N_max][N_max] or NULL, N_max = max_boxes * num_goals + 1: the matrix, its N x N block written (N = n_push * num_goals + 1)
+ * Status: BP_GTSP_OK; BP_GTSP_NOTHING_TO_PUSH (the path is the pose alone); BP_GTSP_SKIPPED (active == 0: nothing but the status is written);
+ * BP_GTSP_CAP (more than max_boxes boxes to push: n_push is written, length 0); BP_GTSP_INVALID (a non-finite pose, goal or counted vertex, or a
+ * count outside 0, 3 .. n_verts: length 0).  BP_GTSP_FLAG_VANISHED: a box to push left nothing when shrunk and was skipped;
+ * BP_GTSP_FLAG_DEGENERATE: a shrunk box touched a goal segment, its route is one point.
+ * BP_EINVAL, with nothing launched or written, for a NULL required pointer, a handle that is not area-clearing, max_boxes outside
+ * 1 .. BP_GTSP_MAX_BOXES, num_goals outside 1 .. BP_GTSP_MAX_GOALS, round_decimals outside 0 .. 15, a negative or non-finite length, speed or scale,
+ * sizes over the caps above, or a workspace that is short or not 16-byte aligned; BP_ESTATE before load and reset.  Reads the handle's device, size
+ * and boundary only.  Enqueued on `stream`; a function of its inputs bit for bit.
+ *
+ * bp_gtsp_track: PlanningBasedPolicy.act after planning.  Per env: past the path's end the action is (0, 0); within switch_dist of waypoint
+ * track_id the id advances (past the end: (0, 0)) and the setpoint becomes that waypoint; then DP.ideal_control: omega = wrap(atan2(yd - y, xd - x)
+ * - yaw) / dt, speed = |R(yaw) (target_speed, 0)|.  actions double [E][2] = (speed / v_scale, omega / w_scale), diag int32 [E] = the id.  An env with
+ * active == 0, a length below 2, a negative id or a non-finite pose or counted waypoint gets NaN actions and diag -1, and its state is left as it is. */
+#define BP_GTSP_MAX_BOXES 12
+#define BP_GTSP_MAX_GOALS 8
+#define BP_GTSP_MAX_SLOTS 64
+enum { BP_GTSP_OK = 0, BP_GTSP_NOTHING_TO_PUSH = 1, BP_GTSP_SKIPPED = 2, BP_GTSP_CAP = 3, BP_GTSP_INVALID = 4,
+       BP_GTSP_FLAG_VANISHED = 0x100, BP_GTSP_FLAG_DEGENERATE = 0x200 };
+typedef struct bp_gtsp_config {
+    double shrink, extend;             /* policy.py: buffer(-0.4), EXTEND_BUFFER = 2 */
+    double lin_vel, ang_vel;           /* transition_graph_lookup.py: 0.5, pi / 4 */
+    double Lfc, dt, target_speed;      /* gtsp_config.yaml controller: 0.5, 0.8, 0.2 */
+    double switch_dist;                /* policy.py act: 0.4 */
+    double v_scale, w_scale;           /* the env's target_speed and max_yaw_rate_step */
+    int32_t round_decimals;            /* np.round(.., 7) */
+    int32_t max_boxes, num_goals;
+    int32_t pad_;
+} bp_gtsp_config;
+int32_t bp_sizeof_gtsp_config(void);
+int64_t bp_gtsp_workspace_bytes(const bp_gtsp_config *cfg, int32_t num_envs);   /* BP_EINVAL (negative) for a config that bp_gtsp_plan refuses */
+int bp_gtsp_plan(bp_handle *h, const bp_gtsp_config *cfg, const double *poses, const double *boxes, const int32_t *counts, int32_t n_boxes,
+                 int32_t n_verts, const double *goals, const uint8_t *active, void *workspace, int64_t workspace_bytes, int32_t *status,
+                 int32_t *n_push, int32_t *tour, int32_t *cost, double *paths, int32_t *lengths, int32_t *track_id, double *track_setpoint,
+                 int32_t *weights, void *stream);
+int bp_gtsp_track(bp_handle *h, const bp_gtsp_config *cfg, const double *paths, const int32_t *lengths, const double *poses, const uint8_t *active,
+                  int32_t *track_id, double *track_setpoint, double *actions, int32_t *diag, void *stream);
+
 const char *bp_last_error(const bp_handle *h);
 int32_t bp_abi_version(void);
 int32_t bp_sizeof_config(void);   /* sizeof(bp_config), so a binding can verify its struct layout */
