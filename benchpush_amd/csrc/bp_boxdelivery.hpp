@@ -1396,7 +1396,8 @@ __global__ __launch_bounds__(256) void k_bd_reset_copy(const DevParams P, const 
     if (tid == 0) {
         Q.nalive[env] = Q.nalive[se]; Q.nprev[env] = Q.nprev[se];
         for (int q = 0; q < 4; q++) { Q.cum[env * 4 + q] = 0.0; Q.cnt[env * 4 + q] = 0; }
-        Q.stepf[(size_t)env * 8 + 4] = 0.0;
+        // robot_hit_obstacle as the settle left it (e_flags of the template slot): area-clearing reads it in its first step, box-delivery clears it there
+        Q.stepf[(size_t)env * 8 + 4] = (B.task == 1) ? (double)D.e_flags[se] : 0.0;
         if (info) {
             double *o = info + (size_t)env * BP_INFO_COUNT;
             const size_t eb = (size_t)env * P.nbcap;

@@ -79,7 +79,8 @@ struct DevPtrs {
     const double *maze_obs_map; // maze: dist_map with the wall raster in the sign bit (wall cells: -1.0), one load per cell for k_observe_maze
     // env state
     int *e_trial, *e_episode, *e_nb, *e_err;   // [record]; e_err: a load ORs the saved bits into the destination, as k_reset_copy does
-    int *e_flags;            // [E] maze: bit0 wall_collision (sticky), bit1 prev_dist valid  [record]
+    int *e_flags;            // [E] maze: bit0 wall_collision (sticky), bit1 prev_dist valid; box-delivery / area-clearing: robot_hit_obstacle as the settle left it
+                             //     (written by k_bd_settle, read from the template slot by k_bd_reset_copy for area-clearing; never read for a live env)  [record]
     double *e_prevdist;      // [E] maze: previous goal-map value  [record]
     unsigned *e_stamp;       // [record]
     double *e_currdt, *e_total_work, *e_ke, *e_imp;   // [record]

@@ -149,6 +149,21 @@ __device__ __forceinline__ void load_state_b(const DevParams &P, const DevPtrs &
             else { v = D.velv[eb + i]; w2 = D.velw[eb + i]; vb = D.velb[eb + i]; }
             mvg = (v.x != 0.0 || v.y != 0.0 || w2.x != 0.0 || w2.y != 0.0 || vb.x != 0.0 || vb.y != 0.0);
             if (KIND == BP_ENV_BOX && i < P.nkin) mvg = true; // the robot is re-cached every sub-step (see substep)
+            // A box that a pre_solve push-out displaced in the LAST sub-step of the previous launch has no velocity and is in nobody's list: inside a launch
+            // substep() re-lists it through S.evmask, which ends with the launch.  Its cached world vertices still belong to the pose before the push-out;
+            // the test repeats the integrate phase's own arithmetic for vertex 0, so an unmoved box reproduces its cache bit for bit and stays out.
+            // Vertex 0 is enough for what exists: the push-outs translate (no rotation), and a translation moves every vertex by the same vector -- one too
+            // small to change vertex 0's doubles could only be missed if it changed another vertex's, i.e. by an ulp.  A handler that rotates would need more.
+            // A delivered box (space.remove: k_bd_finish parks it with an empty AABB) stays out: listing it would give it an AABB and bring it back.
+            if (KIND == BP_ENV_BOX && !mvg && i >= P.nkin) {
+                const double4 ms = gE(E.mass, i), bb = gE(E.bb, i);
+                if (ms.x != 0.0 && bb.x <= bb.z) {
+                    const d2 p = gE(E.pxy, i), r = gE(E.rot, i), lv = gE(E.lv, i * BP_MAXV), wv = gE(E.wv, i * BP_MAXV);
+                    const double tx = p.x - (ms.z * r.x - ms.w * r.y), ty = p.y - (ms.z * r.y + ms.w * r.x);
+                    const double vx = (r.x * lv.x + (-r.y) * lv.y) + tx, vy = (r.y * lv.x + r.x * lv.y) + ty;
+                    mvg = (vx != wv.x || vy != wv.y);
+                }
+            }
         }
         const unsigned long long m = ballot(mvg);
         const unsigned long long ms = ballot(mvg && i >= P.nkin);
@@ -752,6 +767,9 @@ __device__ __forceinline__ bool physics_body(const DevParams &P, const DevPtrs &
             total_work = 0.0;
             D.e_total_work[env] = 0.0;
             D.e_flags[env] = 0; D.e_prevdist[env] = 0.0; // reset() clears wall_collision after the settle (maze_NAMO_env.py:338)
+            // area-clearing keeps robot_hit_obstacle of the settle: reset() clears it before the 1000 sub-steps (area_clearing.py:305,407) and step() only at
+            // its end (:776), so a robot that starts on a wall or a column leaves execute_robot_path of its first step early (k_bd_reset_copy reads this)
+            if (KIND == BP_ENV_BOX) D.e_flags[env] = S.robot_hit;
             if (info) {
                 double *o = info + (size_t)env * BP_INFO_COUNT;
                 for (int k = 0; k < BP_INFO_COUNT; k++) o[k] = 0.0;

@@ -39,7 +39,7 @@ class BatchedAreaClearingEnv(BatchedBoxDeliveryEnv):
     render_task = "area_clearing"
 
 
-    def __init__(self, num_envs, cfg=None, trials=None, device="cuda:0", env_id_offset=0, num_trials=32, base_seed=0):
+    def __init__(self, num_envs, cfg=None, trials=None, device="cuda:0", env_id_offset=0, num_trials=32, base_seed=0, bd_overrides=None):
         if not torch.cuda.is_available():
             raise _lib.BpError("BatchedAreaClearingEnv needs a ROCm GPU (torch.cuda.is_available() is False); no CPU fallback")
         self.L = _lib.load()
@@ -48,6 +48,8 @@ class BatchedAreaClearingEnv(BatchedBoxDeliveryEnv):
         self.device = torch.device(device)
         self.params = area_clearing_physics_params(self.cfg)
         self.bd_params = area_clearing_params(self.cfg)
+        if bd_overrides:   # constants of the reference that are not in its config (e.g. STEP_LIMIT): tests shorten them
+            self.bd_params.update(bd_overrides)
         if trials is None:
             trials = generate_trials(self.cfg, num_trials, base_seed)
         self.trials = trials

@@ -549,6 +549,12 @@ class BatchedShipIceEnv(_BatchedBase):
         _lib.check(self.L, self.h, self.L.bp_get_num_bodies(self.h, out.ctypes.data_as(C.c_void_p)), "bp_get_num_bodies")
         return out
 
+    def error_flags(self):
+        """The in-kernel capacity flags of every env (BP_ERR_* bits, numpy int32 [E]; sticky since load) without raising: what check_errors() tests."""
+        out = np.zeros(self.num_envs, np.int32)
+        self.L.bp_check_errors(self.h, out.ctypes.data_as(C.c_void_p))
+        return out
+
     def check_errors(self):
         out = np.zeros(self.num_envs, np.int32)
         rc = self.L.bp_check_errors(self.h, out.ctypes.data_as(C.c_void_p))

@@ -150,6 +150,12 @@ class OracleBoxDelivery:
         self.L.orc_get_shape_states(self.L.orc_bd_physics(self.h), _p(out))
         return out
 
+    def stats(self):
+        """The physics space's counters since reset (oracle.OracleShipIce.stats): arb_max / ncol_max are the peaks per sub-step of active arbiters / colours."""
+        out = np.zeros(8, np.int64)
+        self.L.orc_get_stats(self.L.orc_bd_physics(self.h), _p(out))
+        return dict(zip(["substeps", "pairs_bb", "narrow", "arb_sum", "arb_max", "moving_sum", "hot_sum", "ncol_max"], out.tolist()))
+
     def alive(self):
         out = np.zeros(self.nbox, np.int32)
         self.L.orc_bd_get_alive(self.h, _p(out))
