@@ -33,7 +33,8 @@ EXPORTS = ["bp_abi_version", "bp_create", "bp_destroy", "bp_load_scenarios", "bp
            "bp_sizeof_lattice_config", "bp_lattice_workspace_bytes", "bp_lattice_search",
            "bp_sizeof_track_config", "bp_track_path",
            "bp_sizeof_rrt_config", "bp_rrt_workspace_bytes", "bp_rrt_uniform", "bp_rrt_plan", "bp_sizeof_track_wp_config", "bp_track_waypoints",
-           "bp_sizeof_gtsp_config", "bp_gtsp_workspace_bytes", "bp_gtsp_plan", "bp_gtsp_track"]
+           "bp_sizeof_gtsp_config", "bp_gtsp_workspace_bytes", "bp_gtsp_plan", "bp_gtsp_track",
+           "bp_bd_step_async", "bp_bd_async_drain", "bp_bd_async_open"]
 GTSP_OK, GTSP_NOTHING_TO_PUSH, GTSP_SKIPPED, GTSP_CAP, GTSP_INVALID = range(5)
 GTSP_STATUS_MASK, GTSP_FLAG_VANISHED, GTSP_FLAG_DEGENERATE = 0xFF, 0x100, 0x200   # status = code | flags
 GTSP_MAX_BOXES, GTSP_MAX_GOALS, GTSP_MAX_SLOTS = 12, 8, 64
@@ -198,6 +199,11 @@ def load():
         L.bp_get_cost_stats.argtypes = [vp, vp, C.c_int32, C.POINTER(C.c_int32)]
     if hasattr(L, "bp_bd_get_cycle_skips"):
         L.bp_bd_get_cycle_skips.argtypes = [vp, vp]
+    if hasattr(L, "bp_bd_step_async"):   # asynchronous step (absent from older builds loaded for same-box comparisons)
+        L.bp_bd_step_async.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.bp_bd_async_drain.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.bp_bd_async_open.argtypes = [vp]
+        L.bp_bd_async_open.restype = C.c_int32
     if hasattr(L, "bp_get_clock_stamps"):
         L.bp_get_clock_stamps.argtypes = [vp, vp]
     if hasattr(L, "bp_sched_warnings"):   # absent from libraries of ABI 6 (tools/ab_bench.sh loads older builds for same-box comparisons)

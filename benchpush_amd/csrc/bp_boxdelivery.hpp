@@ -37,6 +37,8 @@ struct BdParams {
     // Two-pass step: pass 0 runs every env for at most `budget` sim steps (0 = no limit), pass 1 resumes the envs that were not done.
     // The envs that finish in pass 0 -- all but the handful that run into the reference's 10 001-step loops -- go through the finish / robot-map / observe
     // kernels while pass 1 is still running on another stream; `sel_want` tells a tail kernel which of the two groups it serves (-1: every env).
+    // Asynchronous step (bd_physics_body<.., SLICE>): pass 2 = bp_bd_step_async (idle envs start, busy envs resume, `budget` sim steps per call), pass 3 = the drain
+    // (busy envs only, budget 0); the tail kernels run with sel_want 0.
     int budget, pass, sel_want;
     int resume_sel;                     // second pass: 0 = every unfinished env, 1 = those that stopped inside execute_robot_path, 2 = the others (until-still loop)
     int cycle_skip;                     // > 0: the second pass of the two-pass step looks for exact recurrences of the robot's state in execute_robot_path once a path has run this many sim steps, and skips whole periods (bd_physics_body<DAMP, CYC>; BP_BD_CYCLE=0 turns it off)
@@ -65,7 +67,10 @@ struct BdPtrs {
     int *nwp;                       // [E]  [record]
     double *stepf;                  // [E][8] robot_distance, ix, iy, ih, hit, substeps, -, -  [record]
     unsigned char *unfin;           // [E] 1 = the env's sim-step loop hit the budget of pass 0 (its loop state is in rs_i / rs_d) -- written by pass 0 for every env  [no record: loop state of the two-pass step, as rs_i / rs_d]
-    int *rs_i;                      // [E][16] phase, wi, path0, done_turning, dp_valid, sp_one, sim_steps, kcount, have_prev, still_done, total_sub, robot_hit, cycles >> 8
+    //                                 asynchronous step (bd_physics_body<.., SLICE>): 1 = busy between calls, 0 = finished in the last call / idle, 2 = idle env of a drain; the lock-step pass 1
+    //                                 never clears the byte, so opening a slice clears it (bp_bd_step_async)
+    int *rs_i;                      // [E][16] phase, wi, path0, done_turning, dp_valid, sp_one, sim_steps, kcount, have_prev, still_done, total_sub, robot_hit, cycles >> 8, hit_limit,
+    //                                 [14] calls of the asynchronous env step so far, [15] serial number of the asynchronous call that last served the env  [no record: loop state, as unfin]
     double *rs_d;                   // [E][4 + 2 * 64] the controller's doubles (L.ctl) and the until-still loop's previous positions (one d2 per lane)
     unsigned *straggler;            // [4] cumulative: envs resumed by pass 1, envs whose loops ran into STEP_LIMIT, recurrences found in execute_robot_path, sim steps they skipped  [no record: counters of the handle]
     float *dist;                    // [E][SH*SW] spfa scratch  [no record: rewritten before it is read]
@@ -456,8 +461,8 @@ __device__ __forceinline__ void bd_load_bits(const BdParams &B, const BdPtrs &Q,
 // ---------------------------------------------------------------------------------------------------------------------
 // k_bd_plan: one wave per env
 // ---------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_bd_plan(const DevParams P, const DevPtrs D, const BdParams B, const BdPtrs Q,
-                                                const double *__restrict__ actions)
+// (the body of k_bd_plan, shared with the entry of the asynchronous step)
+__device__ __forceinline__ void bd_plan_body(const DevParams &P, const DevPtrs &D, const BdParams &B, const BdPtrs &Q, const double *__restrict__ actions)
 {
     const int env = blockIdx.x;
     const int lane = lane_id();
@@ -524,6 +529,19 @@ __global__ __launch_bounds__(64) void k_bd_plan(const DevParams P, const DevPtrs
         sf[1] = ix; sf[2] = iy; sf[3] = ih;
         if (em) atomicOr(&D.e_err[env], BP_ERR_ARB_OVERFLOW);
     }
+}
+__global__ __launch_bounds__(64) void k_bd_plan(const DevParams P, const DevPtrs D, const BdParams B, const BdPtrs Q,
+                                                const double *__restrict__ actions)
+{
+    bd_plan_body(P, D, B, Q, actions);
+}
+// Asynchronous step (bp_bd_step_async): an idle env takes its action and is planned; a busy env -- in the middle of an env step, Q.unfin == 1 -- keeps the
+// waypoints, the start pose and the spfa scratch of the step it is in.
+__global__ __launch_bounds__(64) void k_bd_plan_async(const DevParams P, const DevPtrs D, const BdParams B, const BdPtrs Q,
+                                                      const double *__restrict__ actions)
+{
+    if (Q.unfin[blockIdx.x] == 1) return;
+    bd_plan_body(P, D, B, Q, actions);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -613,15 +631,36 @@ __device__ __forceinline__ void bd_cycle_skip(unsigned *mvs, double *ctl, const 
 #define BP_BD_WAVES 2
 #endif
 // DAMP: space.damping != 0 (box_delivery_env.py:204, area_clearing.py: `space.damping = cfg.sim.damping`; no shipped config) -> substep<BP_ENV_BOX, true>
-template <bool DAMP, bool CYC = false>
-__device__ __forceinline__ void bd_physics_body(const DevParams &P, const DevPtrs &D, const BdParams &B, const BdPtrs &Q)
+// SLICE: the asynchronous step (bp_bd_step_async / bp_bd_async_drain; k_bd_slice, k_bd_slice_resume).  Every env of the handle is idle or busy; the group byte
+// Q.unfin holds 1 for a busy env -- in the middle of an env step, its loop state in Q.rs_* -- between calls.  A call starts the idle envs (B.pass == 2) or
+// leaves them alone (B.pass == 3, the drain), resumes the busy ones, runs each for at most B.budget sim steps of this call (0: no limit) and writes the group
+// byte again: 0 = the env step ended in this call (the tail kernels serve exactly these with sel_want == 0, and `ready` is 1), 1 = still busy, 2 = did not run
+// (idle env of a drain).  A call is two launches, as pass 1 of the two-pass step: B.resume_sel == 1, the kernel with the recurrence test, serves the busy envs
+// that stopped inside execute_robot_path; B.resume_sel == 2, the lean kernel, serves every other env.  An env served by one launch carries the call's serial
+// number (`epoch`, rs_i[15]) and is left alone by the other.  rs_i[14] counts the calls of the env step; `slices` gets it with the transition.
+template <bool DAMP, bool CYC = false, bool SLICE = false>
+__device__ __forceinline__ void bd_physics_body(const DevParams &P, const DevPtrs &D, const BdParams &B, const BdPtrs &Q, unsigned char *ready = nullptr,
+                                                int *slices = nullptr, const int epoch = 0)
 {
     const int env = (D.order != nullptr) ? D.order[blockIdx.x] : (int)blockIdx.x;
-    const bool resume = B.pass == 1;
+    bool slice_busy = false;
+    if constexpr (SLICE) {
+        int *ri0 = Q.rs_i + (size_t)env * 16;
+        if (ri0[15] == epoch) return;                                     // served by the other launch of this call
+        slice_busy = Q.unfin[env] == 1;
+        if (B.resume_sel != 0 && (slice_busy ? ((ri0[0] == 0) != (B.resume_sel == 1)) : (B.resume_sel == 1))) return;   // the other launch's env (resume_sel 0: one launch)
+        if (!slice_busy && B.pass == 3) {                                 // idle env of a drain: no transition
+            if (lane_id() == 0) { Q.unfin[env] = 2; ready[env] = 0; ri0[15] = epoch; }
+            return;
+        }
+    }
+    const bool resume = SLICE ? slice_busy : (B.pass == 1);
+    if constexpr (!SLICE) {
     if (resume && Q.unfin[env] == 0) return;       // pass 1 serves only the envs that pass 0 left unfinished
     // ... in two launches: the envs that ran out of budget inside execute_robot_path (saved phase 0 = PH_PATH) go to the kernel that holds the recurrence test,
     // the ones inside step_simulation_until_still -- the reference's own 10 001-step loops, which never recur -- stay on the lean kernel
     if (resume && B.resume_sel != 0 && ((Q.rs_i[(size_t)env * 16] == 0) != (B.resume_sel == 1))) return;
+    }
     const unsigned long long t_begin = __builtin_amdgcn_s_memtime();
     const int lane = lane_id();
     LdsCtx L;
@@ -687,6 +726,9 @@ __device__ __forceinline__ void bd_physics_body(const DevParams &P, const DevPtr
     bool cyc_have = false;
     unsigned cyc_costp = 0u;
     unsigned cycles_before = 0u;
+    unsigned sub_entry = 0u;     // SLICE: total_sub counts the whole env step; the budget is about the sim steps of this call
+    int calls = 1;               // SLICE: calls this env step has taken, this one included
+    if constexpr (SLICE) { if (resume) { sub_entry = (unsigned)Q.rs_i[(size_t)env * 16 + 10]; calls = Q.rs_i[(size_t)env * 16 + 14] + 1; } }
     if (resume) {
         // the loop state of pass 0 (the bodies, arbiters and velocities came back through load_state, as after a park of the step scheduler)
         const int *ri = Q.rs_i + (size_t)env * 16;
@@ -934,11 +976,22 @@ __device__ __forceinline__ void bd_physics_body(const DevParams &P, const DevPtr
             if (!still_done && sim_steps > B.step_limit) hit_limit = true;
             if (still_done || sim_steps > B.step_limit) phase = PH_DONE;
         }
+        if constexpr (SLICE) {
+            if (B.budget > 0 && (int)(total_sub - sub_entry) >= B.budget && phase != PH_DONE) break;   // out of this call's budget: the next call carries on from here
+        } else
         if (B.pass == 0 && B.budget > 0 && (int)total_sub >= B.budget && phase != PH_DONE) break;   // out of budget: pass 1 carries on from here
     }
     const bool unfinished = phase != PH_DONE;
     __syncthreads();
     store_state(P, D, L, A, env);
+    if constexpr (SLICE) {
+        if (lane == 0) {
+            Q.unfin[env] = unfinished ? 1 : 0;
+            ready[env] = unfinished ? 0 : 1;
+            Q.rs_i[(size_t)env * 16 + 15] = epoch;
+            if (unfinished) Q.rs_i[(size_t)env * 16 + 14] = calls; else slices[env] = calls;
+        }
+    } else
     if (B.pass == 0 && lane == 0) Q.unfin[env] = unfinished ? 1 : 0;
     if (unfinished) {
         int *ri = Q.rs_i + (size_t)env * 16;
@@ -946,9 +999,9 @@ __device__ __forceinline__ void bd_physics_body(const DevParams &P, const DevPtr
         if (lane == 0) {
             ri[0] = phase; ri[1] = wi; ri[2] = path0; ri[3] = done_turning; ri[4] = dp_valid; ri[5] = sp_one; ri[6] = sim_steps; ri[7] = kcount;
             ri[8] = have_prev; ri[9] = still_done; ri[10] = (int)total_sub; ri[11] = S.robot_hit;
-            ri[12] = (int)((__builtin_amdgcn_s_memtime() - t_begin) >> 8); ri[13] = hit_limit;
+            ri[12] = (int)((__builtin_amdgcn_s_memtime() - t_begin) >> 8) + (SLICE ? (int)cycles_before : 0); ri[13] = hit_limit;
             D.e_stamp[env] = S.stamp; D.e_currdt[env] = S.curr_dt;
-            if (Q.straggler != nullptr) atomicAdd(&Q.straggler[0], 1u);
+            if (!SLICE && Q.straggler != nullptr) atomicAdd(&Q.straggler[0], 1u);
         }
         if (lane < 4) rd[lane] = L.ctl[lane];
         rd[4 + 2 * lane] = prevp.x; rd[4 + 2 * lane + 1] = prevp.y;
@@ -988,6 +1041,24 @@ __global__ __launch_bounds__(64, BP_BD_WAVES) void k_bd_physics_resume(const Dev
 __global__ __launch_bounds__(64, BP_BD_WAVES) void k_bd_physics_damp(const DevParams P, const DevPtrs D, const BdParams B, const BdPtrs Q)
 {
     bd_physics_body<true>(P, D, B, Q);
+}
+// the asynchronous step (bd_physics_body<DAMP, CYC, SLICE = true>): the lean form and the one with the recurrence test, as k_bd_physics / k_bd_physics_resume
+__global__ __launch_bounds__(64, BP_BD_WAVES) void k_bd_slice(const DevParams P, const DevPtrs D, const BdParams B, const BdPtrs Q, unsigned char *__restrict__ ready,
+                                                              int *__restrict__ slices, const int epoch)
+{
+    bd_physics_body<false, false, true>(P, D, B, Q, ready, slices, epoch);
+}
+__global__ __launch_bounds__(64, BP_BD_WAVES) void k_bd_slice_resume(const DevParams P, const DevPtrs D, const BdParams B, const BdPtrs Q, unsigned char *__restrict__ ready,
+                                                                     int *__restrict__ slices, const int epoch)
+{
+    bd_physics_body<false, true, true>(P, D, B, Q, ready, slices, epoch);
+}
+// bp_reset while an asynchronous slice is open: a busy env of the mask is cancelled -- idle again, its half-done env step emits nothing (the reset kernels
+// that follow replace its bodies, counters and waypoints like those of any other env)
+__global__ __launch_bounds__(256) void k_bd_async_cancel(const BdPtrs Q, const unsigned char *__restrict__ mask, const int num_envs)
+{
+    const int env = blockIdx.x * blockDim.x + threadIdx.x;
+    if (env < num_envs && mask[env] != 0 && Q.unfin[env] == 1) Q.unfin[env] = 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -58,6 +58,9 @@ struct bp_handle {
     hipStream_t st_aux3 = nullptr;  // ... pass 1's kernel with the recurrence test of execute_robot_path, beside the lean one
     hipEvent_t ev_join3 = nullptr;
     int bd_budget = 0;              // sim steps of pass 0 of the two-pass step, 0 = one pass (BP_BD_BUDGET)
+    // asynchronous step of box-delivery / area-clearing (bp_bd_step_async / bp_bd_async_drain)
+    bool async_open = false;        // a slice is open: envs may be in the middle of an env step (host flag; set by bp_bd_step_async, cleared by the drain and by a reset of all envs)
+    int as_epoch = 0;               // serial number of the last asynchronous call (the two launches of a call tell each other's envs apart by it)
     DevParams P;
     DevPtrs D;
     std::vector<void *> allocs;
@@ -863,8 +866,28 @@ __global__ __launch_bounds__(256) void k_episode_metrics(const DevParams P, cons
     }
 }
 
+enum { MODE_ASYNC = 2, MODE_DRAIN = 3 };   // box-delivery / area-clearing: bp_bd_step_async, bp_bd_async_drain
+struct AsyncArgs {                         // what those two calls hand to launch() beside the step's outputs
+    int budget;                            // sim steps per env and call (0: no limit, the drain)
+    unsigned char *ready;                  // [E]
+    int *slices;                           // [E]
+};
+// The side streams and events of a box-delivery / area-clearing step, created when first needed: the robot map beside the finish kernel (st_aux, ev_fork,
+// ev_join); two_pass: also those of the second pass of the two-pass step.
+static int bd_side_streams(bp_handle *h, bool two_pass)
+{
+    if (!h->st_aux) HIPCHK(h, hipStreamCreateWithFlags(&h->st_aux, hipStreamNonBlocking));
+    if (!h->ev_fork) HIPCHK(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
+    if (!h->ev_join) HIPCHK(h, hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
+    if (!two_pass) return BP_OK;
+    if (!h->st_aux2) HIPCHK(h, hipStreamCreateWithFlags(&h->st_aux2, hipStreamNonBlocking));
+    if (!h->ev_join2) HIPCHK(h, hipEventCreateWithFlags(&h->ev_join2, hipEventDisableTiming));
+    if (!h->st_aux3) HIPCHK(h, hipStreamCreateWithFlags(&h->st_aux3, hipStreamNonBlocking));
+    if (!h->ev_join3) HIPCHK(h, hipEventCreateWithFlags(&h->ev_join3, hipEventDisableTiming));
+    return BP_OK;
+}
 static int launch(bp_handle *h, int mode, const double *actions, const unsigned char *mask, unsigned char *obs, double *reward,
-                  unsigned char *term, unsigned char *trunc, double *info, hipStream_t st, bool physics, bool raster)
+                  unsigned char *term, unsigned char *trunc, double *info, hipStream_t st, bool physics, bool raster, const AsyncArgs *as = nullptr)
 {
     hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
     if (h->timing) {
@@ -887,15 +910,7 @@ static int launch(bp_handle *h, int mode, const double *actions, const unsigned 
                 h->steps_done = true;
                 hipLaunchKernelGGL(k_bd_plan, dim3(E), dim3(64), h->bd_lds, st, h->P, h->D, h->B, h->Q, actions);
                 HIPCHK(h, hipGetLastError());
-                if (!h->st_aux) {
-                    HIPCHK(h, hipStreamCreateWithFlags(&h->st_aux, hipStreamNonBlocking));
-                    HIPCHK(h, hipStreamCreateWithFlags(&h->st_aux2, hipStreamNonBlocking));
-                    HIPCHK(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-                    HIPCHK(h, hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-                    HIPCHK(h, hipEventCreateWithFlags(&h->ev_join2, hipEventDisableTiming));
-                    HIPCHK(h, hipStreamCreateWithFlags(&h->st_aux3, hipStreamNonBlocking));
-                    HIPCHK(h, hipEventCreateWithFlags(&h->ev_join3, hipEventDisableTiming));
-                }
+                if (int rc = bd_side_streams(h, true)) return rc;
                 auto finish = [&](const BdParams &Bx, hipStream_t s_) {
                     if (h->B.task == 1) hipLaunchKernelGGL(k_ac_finish, dim3(E), dim3(64), h->bd_lds, s_, h->P, h->D, Bx, h->Q, 0, 0, reward, term, trunc, info);
                     else hipLaunchKernelGGL(k_bd_finish, dim3(E), dim3(64), h->bd_lds, s_, h->P, h->D, Bx, h->Q, 0, 0, reward, term, trunc, info);
@@ -966,6 +981,41 @@ static int launch(bp_handle *h, int mode, const double *actions, const unsigned 
                 HIPCHK(h, hipGetLastError());
                 HIPCHK(h, hipStreamWaitEvent(st, h->ev_join, 0));
                 }
+            } else if (mode == MODE_ASYNC || mode == MODE_DRAIN) {
+                // Asynchronous step (bp_bd_step_async / bp_bd_async_drain, DESIGN.md "Asynchronous step"): idle envs are planned and started, busy ones resumed, each
+                // runs at most `as->budget` sim steps; the envs whose env step ended (group byte 0) go through the tail kernels exactly as in the one-pass step.
+                // (Dispatch order: h->D.order is what the last lock-step step left, or none -- any permutation serves.)
+                if (int rc = bd_side_streams(h, false)) return rc;
+                const int epoch = ++h->as_epoch;
+                BdParams Bp = h->B, Bl = h->B, Bt = h->B;
+                Bp.pass = Bl.pass = (mode == MODE_ASYNC) ? 2 : 3;
+                Bp.budget = Bl.budget = (mode == MODE_ASYNC) ? as->budget : 0;
+                Bp.resume_sel = 1; Bl.resume_sel = 2; Bt.sel_want = 0;
+                if (mode == MODE_ASYNC) {
+                    hipLaunchKernelGGL(k_bd_plan_async, dim3(E), dim3(64), h->bd_lds, st, h->P, h->D, h->B, h->Q, actions);
+                    HIPCHK(h, hipGetLastError());
+                }
+                // first the busy envs that stopped inside execute_robot_path (the kernel with the recurrence test), then every other env on the lean kernel
+                if (h->B.cycle_skip > 0) {
+                    hipLaunchKernelGGL(k_bd_slice_resume, dim3(E), dim3(64), h->lds_bytes, st, h->P, h->D, Bp, h->Q, as->ready, as->slices, epoch);
+                    HIPCHK(h, hipGetLastError());
+                } else Bl.resume_sel = 0;
+                hipLaunchKernelGGL(k_bd_slice, dim3(E), dim3(64), h->lds_bytes, st, h->P, h->D, Bl, h->Q, as->ready, as->slices, epoch);
+                HIPCHK(h, hipGetLastError());
+                HIPCHK(h, hipEventRecord(h->ev_fork, st));
+                HIPCHK(h, hipStreamWaitEvent(h->st_aux, h->ev_fork, 0));
+                hipLaunchKernelGGL(k_bd_robot_map, dim3(E), dim3(BDR_THREADS), h->bd_rmap_lds, h->st_aux, h->P, h->D, Bt, h->Q, 0);
+                HIPCHK(h, hipGetLastError());
+                HIPCHK(h, hipEventRecord(h->ev_join, h->st_aux));
+                if (h->B.task == 1) hipLaunchKernelGGL(k_ac_finish, dim3(E), dim3(64), h->bd_lds, st, h->P, h->D, Bt, h->Q, 0, 0, reward, term, trunc, info);
+                else hipLaunchKernelGGL(k_bd_finish, dim3(E), dim3(64), h->bd_lds, st, h->P, h->D, Bt, h->Q, 0, 0, reward, term, trunc, info);
+                HIPCHK(h, hipGetLastError());
+                HIPCHK(h, hipStreamWaitEvent(st, h->ev_join, 0));
+                if (raster && obs) {
+                    hipLaunchKernelGGL(k_bd_observe, dim3(E), dim3(BDO_THREADS), h->bd_obs_lds, st, h->P, h->D, Bt, h->Q, (const unsigned char *)nullptr, obs);
+                    HIPCHK(h, hipGetLastError());
+                }
+                raster = false;   // only the envs that emitted a transition get a new observation
             } else {
                 hipLaunchKernelGGL(k_reset_copy, dim3(E), dim3(256), 0, st, h->P, h->D, mask, (double *)nullptr);
                 HIPCHK(h, hipGetLastError());
@@ -1115,11 +1165,16 @@ int bp_reset(bp_handle *h, const uint8_t *env_mask, uint8_t *obs, double *info, 
     if (!h) return BP_EINVAL;
     if (!h->loaded) return fail(h, BP_ESTATE, "bp_load_scenarios has not been called");
     BP_DEVICE(h);
+    if (h->async_open && env_mask != nullptr) {   // an asynchronous slice is open: the busy envs of the mask are cancelled (a reset of all envs closes the slice instead)
+        hipLaunchKernelGGL(k_bd_async_cancel, dim3((h->num_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->Q, env_mask, h->num_envs);
+        HIPCHK(h, hipGetLastError());
+    }
     const bool save = h->timing;
     h->timing = false; // resets are not part of the per-step kernel timing
     const int rc = launch(h, MODE_RESET, nullptr, env_mask, obs, nullptr, nullptr, nullptr, info, (hipStream_t)stream, true, true);
     h->timing = save;
     if (rc == BP_OK) h->was_reset = true;
+    if (rc == BP_OK && env_mask == nullptr) h->async_open = false;
     return rc;
 }
 
@@ -1128,6 +1183,7 @@ int bp_step(bp_handle *h, const double *actions, uint8_t *obs, double *reward, u
 {
     if (!h || !actions) return BP_EINVAL;
     if (!h->loaded || !h->was_reset) return fail(h, BP_ESTATE, "bp_step before bp_load_scenarios/bp_reset");
+    if (h->async_open) return fail(h, BP_ESTATE, "bp_step while an asynchronous slice is open (bp_bd_async_drain or a reset of all envs closes it)");
     BP_DEVICE(h);
     return launch(h, MODE_STEP, actions, nullptr, obs, reward, terminated, truncated, info, (hipStream_t)stream, true, true);
 }
@@ -1137,9 +1193,59 @@ int bp_step_physics(bp_handle *h, const double *actions, double *reward, uint8_t
 {
     if (!h || !actions) return BP_EINVAL;
     if (!h->loaded || !h->was_reset) return fail(h, BP_ESTATE, "bp_step_physics before bp_load_scenarios/bp_reset");
+    if (h->async_open) return fail(h, BP_ESTATE, "bp_step_physics while an asynchronous slice is open (bp_bd_async_drain or a reset of all envs closes it)");
     BP_DEVICE(h);
     return launch(h, MODE_STEP, actions, nullptr, nullptr, reward, terminated, truncated, info, (hipStream_t)stream, true, false);
 }
+
+// ---- asynchronous step of box-delivery / area-clearing (DESIGN.md "Asynchronous step") ----
+static int async_ready(bp_handle *h, const char *what)
+{
+    if (!h->loaded || !h->was_reset) return fail(h, BP_ESTATE, std::string(what) + " before bp_bd_load / bp_reset");
+    if (h->P.env_kind != BP_ENV_BOX || h->Q.unfin == nullptr) return fail(h, BP_EINVAL, std::string(what) + ": not a box-delivery / area-clearing handle (the steps of the other environments have a fixed length)");
+    if (h->damp) return fail(h, BP_EINVAL, std::string(what) + ": handles with sim.damping != 0 have no asynchronous step");
+    return BP_OK;
+}
+
+int bp_bd_step_async(bp_handle *h, const double *actions, int32_t budget, uint8_t *obs, double *reward, uint8_t *terminated, uint8_t *truncated,
+                     double *info, uint8_t *ready, int32_t *slices, void *stream)
+{
+    if (!h || !actions || !reward || !terminated || !truncated || !info || !ready || !slices) return BP_EINVAL;
+    if (int rc = async_ready(h, "bp_bd_step_async")) return rc;
+    if (budget < 1) return fail(h, BP_EINVAL, "bp_bd_step_async: budget < 1 sim step");
+    BP_DEVICE(h);
+    if (!h->async_open) {
+        // every env is idle.  The lock-step second pass never clears the group byte, and a drain leaves 2 in it: clear on opening
+        HIPCHK(h, hipMemsetAsync(h->Q.unfin, 0, (size_t)h->num_envs, (hipStream_t)stream));
+        if (h->as_epoch > 0x7FFF0000) {   // (serial numbers start over long before they wrap)
+            HIPCHK(h, hipMemsetAsync(h->Q.rs_i, 0, sizeof(int) * 16 * (size_t)h->num_envs, (hipStream_t)stream));
+            h->as_epoch = 0;
+        }
+    }
+    // open before anything of the call is enqueued: should the call fail part-way, envs may already be busy, and the handle must refuse bp_step / bp_save_state
+    // until a drain or a reset of all envs
+    h->async_open = true;
+    const AsyncArgs as = {budget, ready, slices};
+    return launch(h, MODE_ASYNC, actions, nullptr, obs, reward, terminated, truncated, info, (hipStream_t)stream, true, true, &as);
+}
+
+int bp_bd_async_drain(bp_handle *h, uint8_t *obs, double *reward, uint8_t *terminated, uint8_t *truncated, double *info, uint8_t *ready,
+                      int32_t *slices, void *stream)
+{
+    if (!h || !reward || !terminated || !truncated || !info || !ready || !slices) return BP_EINVAL;
+    if (int rc = async_ready(h, "bp_bd_async_drain")) return rc;
+    BP_DEVICE(h);
+    if (!h->async_open) {   // no env is busy: nothing to finish
+        HIPCHK(h, hipMemsetAsync(ready, 0, (size_t)h->num_envs, (hipStream_t)stream));
+        return BP_OK;
+    }
+    const AsyncArgs as = {0, ready, slices};
+    const int rc = launch(h, MODE_DRAIN, nullptr, nullptr, obs, reward, terminated, truncated, info, (hipStream_t)stream, true, true, &as);
+    if (rc == BP_OK) h->async_open = false;
+    return rc;
+}
+
+int32_t bp_bd_async_open(bp_handle *h) { return (h && h->async_open) ? 1 : 0; }
 
 int bp_observe(bp_handle *h, const uint8_t *env_mask, uint8_t *obs, void *stream)
 {
@@ -1881,9 +1987,12 @@ int bp_bd_load(bp_handle *h, int32_t T, int32_t nbox, const double *starts, cons
     HIPCHK(h, hipFuncSetAttribute((const void *)k_bd_physics, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
     HIPCHK(h, hipFuncSetAttribute((const void *)k_bd_physics_resume, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
     HIPCHK(h, hipFuncSetAttribute((const void *)k_bd_physics_damp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
+    HIPCHK(h, hipFuncSetAttribute((const void *)k_bd_slice, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
+    HIPCHK(h, hipFuncSetAttribute((const void *)k_bd_slice_resume, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
     HIPCHK(h, hipFuncSetAttribute((const void *)k_bd_settle_damp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
     h->damp = h->P.damping_pow != 0.0;   // space.damping != 0: the generic instantiations (substep<BP_ENV_BOX, DAMP = true>)
     HIPCHK(h, hipFuncSetAttribute((const void *)k_bd_plan, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->bd_lds));
+    HIPCHK(h, hipFuncSetAttribute((const void *)k_bd_plan_async, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->bd_lds));
     HIPCHK(h, hipFuncSetAttribute((const void *)k_bd_finish, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->bd_lds));
     HIPCHK(h, hipFuncSetAttribute((const void *)k_ac_finish, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->bd_lds));
     HIPCHK(h, hipFuncSetAttribute((const void *)k_bd_observe, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->bd_obs_lds));
@@ -2115,6 +2224,7 @@ int bp_save_state(bp_handle *h, const int32_t *env_ids, int32_t k, uint8_t *reco
 {
     if (!h) return BP_EINVAL;
     if (int rc = state_ready(h, "bp_save_state")) return rc;
+    if (h->async_open) return fail(h, BP_ESTATE, "bp_save_state while an asynchronous slice is open: state records do not carry the loop state of a busy env");
     if (!env_ids || !records || k <= 0 || ((uintptr_t)records & 15u)) return fail(h, BP_EINVAL, "bp_save_state: null env_ids / records, k <= 0 or records not 16-byte aligned");
     BP_DEVICE(h);
     if (int rc = state_check_ids(h, "bp_save_state", env_ids, nullptr, k, (hipStream_t)stream, nullptr)) return rc;
@@ -2125,6 +2235,7 @@ int bp_load_state(bp_handle *h, const int32_t *env_ids, int32_t k, const uint8_t
 {
     if (!h) return BP_EINVAL;
     if (int rc = state_ready(h, "bp_load_state")) return rc;
+    if (h->async_open) return fail(h, BP_ESTATE, "bp_load_state while an asynchronous slice is open: state records do not carry the loop state of a busy env");
     if (!env_ids || !records || k <= 0 || ((uintptr_t)records & 15u)) return fail(h, BP_EINVAL, "bp_load_state: null env_ids / records, k <= 0 or records not 16-byte aligned");
     BP_DEVICE(h);
     if (!(flags & BP_STATE_TRUSTED))
@@ -2136,6 +2247,7 @@ int bp_clone_state(bp_handle *h, const int32_t *src_ids, const int32_t *dst_ids,
 {
     if (!h) return BP_EINVAL;
     if (int rc = state_ready(h, "bp_clone_state")) return rc;
+    if (h->async_open) return fail(h, BP_ESTATE, "bp_clone_state while an asynchronous slice is open: state records do not carry the loop state of a busy env");
     if (!src_ids || !dst_ids || k <= 0) return fail(h, BP_EINVAL, "bp_clone_state: null ids or k <= 0");
     BP_DEVICE(h);
     if (!(flags & BP_STATE_TRUSTED))

@@ -34,7 +34,8 @@ def _ac_cfg(cfg):
 
 
 class BatchedAreaClearingEnv(BatchedBoxDeliveryEnv):
-    """E independent area-clearing environments on one GPU: reset(mask) / step(actions) with device tensors."""
+    """E independent area-clearing environments on one GPU: reset(mask) / step(actions) with device tensors; step_async(actions, budget) / drain() /
+    async_open / slices, the asynchronous step, are BatchedBoxDeliveryEnv's (the two tasks share the step kernels)."""
 
     render_task = "area_clearing"
 
@@ -82,6 +83,12 @@ class BatchedAreaClearingEnv(BatchedBoxDeliveryEnv):
         self._actions = torch.zeros(self.num_envs * self.action_dim, dtype=torch.float64, device=self.device)
         self.target_speed = float(self.cfg.controller.target_speed)     # area_clearing.py:196-209: what a 'velocity' action is scaled by
         self.max_yaw_rate_step = (np.pi / 2) / 15
+
+    ASYNC_BUDGET = 3000   # the best of the measured sweep for this task (profiles/async/README.md: its env steps have no stragglers, so slicing only adds launches)
+
+    def step_async(self, actions, budget=ASYNC_BUDGET):
+        """BatchedBoxDeliveryEnv.step_async with this task's default budget."""
+        return super().step_async(actions, budget)
 
     # -- the planning baseline's device calls (DESIGN.md "GTSP") --------------------------------------------
     def _need(self, fn, t, name, dtypes, shape):

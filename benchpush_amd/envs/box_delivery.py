@@ -92,6 +92,53 @@ class BatchedBoxDeliveryEnv(BatchedShipIceEnv):
                                                  _ptr(self.truncated), _ptr(self.info), self._stream()), "bp_step")
         return self.obs, self.reward, self.terminated, self.truncated, self.info
 
+    # -- asynchronous step (DESIGN.md "Asynchronous step") -------------------------------------------------
+    ASYNC_BUDGET = 500    # default budget of step_async in sim steps: the best of the measured sweep 500 / 1000 / 2000 / 3000 at 4096 envs (profiles/async/README.md)
+
+    def _async_io(self):
+        if getattr(self, "_ready", None) is None:
+            self._ready = torch.zeros(self.num_envs, dtype=torch.uint8, device=self.device)
+            self._slices = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
+        return self._ready, self._slices
+
+    @property
+    def slices(self):
+        """int32 [E] on the device: how many step_async / drain calls the transition an env emitted last took."""
+        return self._async_io()[1]
+
+    @property
+    def async_open(self):
+        """True from a step_async until a drain() or a reset of all envs: envs may be in the middle of an env step (a host flag, no device read)."""
+        return bool(self.L.bp_bd_async_open(self.h))
+
+    def step_async(self, actions, budget=ASYNC_BUDGET):
+        """Opt-in asynchronous step: every env is idle or busy (in the middle of an env step).  An idle env takes its row of `actions` (shaped as for step) and
+        starts an env step, a busy env ignores its row and resumes; every env then runs at most `budget` >= 1 sim steps.  Returns (obs, reward, terminated,
+        truncated, info, ready): ready is uint8 [E] on the device; an env with ready[e] = 1 finished its env step in this call, wrote its rows exactly as step()
+        would have and is idle again (``slices[e]`` = calls the step took); the rows of every other env are untouched and its step goes on in the next call.
+        The transitions an env emits do not depend on the budget or on the other envs: they are step()'s for the actions the env accepted, bit for bit.  What
+        does depend on them is which envs emit: short env steps are sampled more often than long ones.  Nothing synchronises with the host.  While a slice is
+        open step(), save_state, restore_state and clone_envs raise BpError; reset(mask) cancels the busy envs of the mask.  Raises BpError, with nothing
+        launched, for budget < 1, actions of the wrong size and configs with sim.damping != 0."""
+        budget = int(budget)
+        if budget < 1:
+            raise _lib.BpError("step_async failed: BP_EINVAL (-1) budget %d < 1 sim step" % budget)
+        if not isinstance(actions, torch.Tensor) or actions.numel() != self._actions.numel() or actions.is_complex():
+            raise _lib.BpError("step_async failed: BP_EINVAL (-1) actions must be a real tensor of %d elements" % self._actions.numel())
+        ready, slices = self._async_io()   # (a config with sim.damping != 0 is refused by the library, before it launches anything)
+        self._actions.copy_(actions.reshape(-1).to(self.device), non_blocking=True)
+        _lib.check(self.L, self.h, self.L.bp_bd_step_async(self.h, _ptr(self._actions), budget, _ptr(self.obs), _ptr(self.reward), _ptr(self.terminated),
+                                                           _ptr(self.truncated), _ptr(self.info), _ptr(ready), _ptr(slices), self._stream()), "bp_bd_step_async")
+        return self.obs, self.reward, self.terminated, self.truncated, self.info, ready
+
+    def drain(self):
+        """Runs the busy envs, and only those, to the end of their env steps (no budget) and closes the slice; returns the six-tuple of step_async with `ready`
+        marking the envs it finished.  Idle envs do nothing and emit nothing.  Afterwards step(), save_state, restore_state and clone_envs work again."""
+        ready, slices = self._async_io()
+        _lib.check(self.L, self.h, self.L.bp_bd_async_drain(self.h, _ptr(self.obs), _ptr(self.reward), _ptr(self.terminated), _ptr(self.truncated),
+                                                            _ptr(self.info), _ptr(ready), _ptr(slices), self._stream()), "bp_bd_async_drain")
+        return self.obs, self.reward, self.terminated, self.truncated, self.info, ready
+
     def stragglers(self):
         """(env steps finished by the second pass of the two-pass step, env steps whose path / until-still loop ran into STEP_LIMIT), cumulative since load."""
         out = np.zeros(2, np.uint32)
@@ -116,7 +163,8 @@ class BatchedBoxDeliveryEnv(BatchedShipIceEnv):
         return out
 
     def box_state(self):
-        """(alive uint8 [E, 24], waypoints [E, 64, 3], number of waypoints [E]) of the last step (host copies)."""
+        """(alive uint8 [E, 24], waypoints [E, 64, 3], number of waypoints [E]) of the last step (host copies).  While an asynchronous slice is open a
+        busy env shows the waypoints of the env step it is in, and the alive flags from before that step."""
         alive = np.zeros((self.num_envs, _lib.BD_MAXBOX), np.uint8)
         wp = np.zeros((self.num_envs, _lib.BD_MAXWP, 3), np.float64)
         nwp = np.zeros(self.num_envs, np.int32)

@@ -234,7 +234,8 @@ class BatchedShipIceEnv(_BatchedBase):
         return self._gobs
 
     def world_polys(self):
-        """info['obs'] for every env: (verts [E, nb_cap, 20, 2] f64, counts [E, nb_cap] i32); index 0 is the ship."""
+        """info['obs'] for every env: (verts [E, nb_cap, 20, 2] f64, counts [E, nb_cap] i32); index 0 is the ship.  (Box-delivery / area-clearing with an
+        asynchronous slice open: a busy env is shown in the middle of its env step.)"""
         out = torch.zeros((self.num_envs, self.nb_cap, _lib.MAXV, 2), dtype=torch.float64, device=self.device)
         cnt = torch.zeros((self.num_envs, self.nb_cap), dtype=torch.int32, device=self.device)
         _lib.check(self.L, self.h, self.L.bp_get_world_polys(self.h, _ptr(out), _ptr(cnt), self._stream()), "bp_get_world_polys")
@@ -269,7 +270,8 @@ class BatchedShipIceEnv(_BatchedBase):
 
     def render_frames(self, env_ids=None, scale=None, paths=None, out=None):
         """rgb_array frames of the envs `env_ids` (None: all): device uint8 [k, H, W, 3] (render.py states the frame).  paths: None or a list of k
-        polylines (arrays [n, >= 2] of world points, or None), drawn as the planned path.  `out` may be a preallocated [k, H, W, 3] uint8 tensor."""
+        polylines (arrays [n, >= 2] of world points, or None), drawn as the planned path.  `out` may be a preallocated [k, H, W, 3] uint8 tensor.  (Box-delivery /
+        area-clearing with an asynchronous slice open: a busy env is drawn in the middle of its env step.)"""
         from .. import render as R
         self._upload_render_table()
         task = R.task_of(self)

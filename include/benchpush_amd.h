@@ -356,6 +356,24 @@ int32_t bp_bd_budget(bp_handle *h);
  * The test runs in the second pass of the two-pass step (k_bd_physics_resume: the envs that ran out of the first pass's sim-step budget, BP_BD_BUDGET -- the kernel every
  * env runs stays lean); BP_BD_CYCLE=<n> at load time: only once a path has run n sim steps, 0: every sim step is run. */
 int bp_bd_get_cycle_skips(bp_handle *h, uint32_t *out2_host);
+/* Asynchronous step of box-delivery / area-clearing handles (opt-in; bp_step is unchanged).  Every env is idle or busy, busy = in the middle of an env step
+ * with its loop state on the device.  bp_bd_step_async: an idle env takes its row of `actions` (shaped as for bp_step), is planned and starts an env step; a
+ * busy env ignores its row and resumes; every env then runs at most `budget` >= 1 sim steps.  An env whose env step ends in the call writes its rows of obs /
+ * reward / terminated / truncated / info exactly as bp_step does, gets ready[e] = 1 and slices[e] = the number of calls the env step took, and is idle again;
+ * every other env gets ready[e] = 0, its rows (slices[e] included) are not touched, and its env step continues in the next call.  ready is uint8 [E], slices
+ * int32 [E], both on the device.  The transitions an env emits are those of bp_step for the actions it accepted, bit for bit, whatever the budget, the other
+ * envs or the cut of the calls.  bp_bd_async_drain runs the busy envs, and only those, to the end of their env steps (same outputs; idle envs emit nothing)
+ * and closes the slice.  While a slice is open -- from a bp_bd_step_async to a drain or a bp_reset of all envs (env_mask NULL) -- bp_step, bp_step_physics,
+ * bp_save_state, bp_load_state and bp_clone_state return BP_ESTATE with nothing touched (state records do not carry the loop state); bp_reset with a mask
+ * cancels the busy envs of the mask (no transition for the half-done env step) and starts their next trials as usual; read-only calls show a busy env
+ * mid-step.  bp_bd_async_open returns 1 while a slice is open (a host flag).  Nothing synchronises; all work is enqueued on `stream`.
+ * BP_EINVAL: NULL handle or tensor (obs may be NULL: no observations), budget < 1, a handle of another environment, or one with damping != 0;
+ * BP_ESTATE before load and reset.  (Added within ABI 11: the additions only add.) */
+int bp_bd_step_async(bp_handle *h, const double *actions, int32_t budget, uint8_t *obs, double *reward, uint8_t *terminated, uint8_t *truncated,
+                     double *info, uint8_t *ready, int32_t *slices, void *stream);
+int bp_bd_async_drain(bp_handle *h, uint8_t *obs, double *reward, uint8_t *terminated, uint8_t *truncated, double *info, uint8_t *ready,
+                      int32_t *slices, void *stream);
+int32_t bp_bd_async_open(bp_handle *h);
 /* tests: per-env box bookkeeping, host buffers: alive uint8 [E][24], waypoints double [E][64][3], nwp int32 [E] (synchronises) */
 int bp_bd_get_state(bp_handle *h, uint8_t *alive, double *waypoints, int32_t *nwp);
 
