@@ -34,7 +34,7 @@ EXPORTS = ["bp_abi_version", "bp_create", "bp_destroy", "bp_load_scenarios", "bp
            "bp_sizeof_track_config", "bp_track_path",
            "bp_sizeof_rrt_config", "bp_rrt_workspace_bytes", "bp_rrt_uniform", "bp_rrt_plan", "bp_sizeof_track_wp_config", "bp_track_waypoints",
            "bp_sizeof_gtsp_config", "bp_gtsp_workspace_bytes", "bp_gtsp_plan", "bp_gtsp_track",
-           "bp_bd_step_async", "bp_bd_async_drain", "bp_bd_async_open"]
+           "bp_bd_step_async", "bp_bd_async_drain", "bp_bd_async_open", "bp_bd_get_episode_boxes", "bp_bd_get_completed", "bp_task_metric_row"]
 GTSP_OK, GTSP_NOTHING_TO_PUSH, GTSP_SKIPPED, GTSP_CAP, GTSP_INVALID = range(5)
 GTSP_STATUS_MASK, GTSP_FLAG_VANISHED, GTSP_FLAG_DEGENERATE = 0xFF, 0x100, 0x200   # status = code | flags
 GTSP_MAX_BOXES, GTSP_MAX_GOALS, GTSP_MAX_SLOTS = 12, 8, 64
@@ -120,7 +120,7 @@ class BpBdConfig(C.Structure):
                 ("pushing_mult", C.c_double), ("distance_scale_max", C.c_double), ("boundary", (C.c_double * 2) * 8),
                 ("outer_boundary", (C.c_double * 2) * 8), ("footprint_verts", (C.c_double * 2) * 4), ("goal_points", (C.c_double * 2) * 128),
                 ("box_half", C.c_double), ("box_density", C.c_double), ("robot_verts", (C.c_double * 2) * 4),
-                ("wheel_verts", ((C.c_double * 2) * 4) * 4), ("bumper_verts", (C.c_double * 2) * 4)]
+                ("wheel_verts", ((C.c_double * 2) * 4) * 4), ("bumper_verts", (C.c_double * 2) * 4), ("robot_mass", C.c_double)]
 
 
 class BpError(RuntimeError):
@@ -204,6 +204,10 @@ def load():
         L.bp_bd_async_drain.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.bp_bd_async_open.argtypes = [vp]
         L.bp_bd_async_open.restype = C.c_int32
+    if hasattr(L, "bp_task_metric_row"):   # episode metrics of box handles (absent from older builds loaded for same-box comparisons)
+        L.bp_bd_get_episode_boxes.argtypes = [vp, vp, vp]
+        L.bp_bd_get_completed.argtypes = [vp, vp]
+        L.bp_task_metric_row.argtypes = [C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, vp]
     if hasattr(L, "bp_get_clock_stamps"):
         L.bp_get_clock_stamps.argtypes = [vp, vp]
     if hasattr(L, "bp_sched_warnings"):   # absent from libraries of ABI 6 (tools/ab_bench.sh loads older builds for same-box comparisons)
@@ -214,7 +218,8 @@ def load():
     L.bp_set_resettle.argtypes = [vp, C.c_int32]
     L.bp_debug_prof.argtypes = [vp, vp]
     L.bp_bd_sizeof_config.restype = C.c_int32
-    if L.bp_bd_sizeof_config() != C.sizeof(BpBdConfig):
+    # (a build from before the episode metrics of these handles, loaded for a same-box comparison, has no robot_mass at the end and reads the rest)
+    if L.bp_bd_sizeof_config() not in (C.sizeof(BpBdConfig), C.sizeof(BpBdConfig) - (0 if hasattr(L, "bp_task_metric_row") else 8)):
         raise BpError("bp_bd_config layout mismatch between _lib.BpBdConfig and the library")
     L.bp_bd_create.argtypes = [C.POINTER(BpBdConfig), C.c_int32, C.c_int64, C.c_int32, C.POINTER(vp)]
     L.bp_bd_load.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, vp, vp]
@@ -337,6 +342,7 @@ def make_bd_config(phys, bd, cfg):
             if k in fields:
                 setattr(c, k, v)
     c.ctrl_dt = float(phys["dt"])
+    c.robot_mass = float(cfg.agent.mass)     # TaskDrivenMetric(robot_mass=cfg.agent.mass) in the reference's baselines
     if bd.get("task", 0) == 1:      # area-clearing: boxes are squares of half-size obstacle_size, density sim.obstacle_density
         c.box_half = float(cfg.obstacle_size)
         c.box_density = float(cfg.sim.obstacle_density)

@@ -2,7 +2,8 @@
 batched env.  Every env gets a push plan at the start of its episode -- one push path per box and boundary goal, the integer transition costs of the
 reference's GTSP instance, and the optimal tour by an exact set DP where the reference calls the GLNS heuristic (``BatchedAreaClearingEnv.gtsp_plan``) --
 and the reference's controller follows it, one launch per step for all envs (``BatchedAreaClearingEnv.track_pushes``).  DESIGN.md "GTSP" lists where
-this deviates from the reference.  How well the baseline clears the area has not been measured.
+this deviates from the reference.  ``evaluate`` with num_envs > 1 scores the envs side by side from the on-device episode metrics
+(examples/eval_task_metrics.py prints the means).
 """
 from typing import List, Tuple
 
@@ -72,10 +73,18 @@ class PlanningBasedPolicy(BasePolicy):
         self._out = env.track_pushes(self.plan, self.tracker, config=cfg, out=self._out)
         return torch.nan_to_num(self._out[0], nan=0.0)      # an env without a path to follow (nothing to push, CAP, INVALID) stands still
 
-    def evaluate(self, num_eps: int, model_eps: str = "latest") -> Tuple[List[float], List[float], List[float], List[float], str]:
-        """The reference's loop on the reference-shaped single env, with action_type 'velocity' and sim.t_max = `t_max`: plan where an episode begins,
-        steer, step, and feed ``TaskDrivenMetric``.  Planner, controller and simulation run on the device.  Returns (success rates, efficiency
-        scores, effort scores, rewards, 'GTSP')."""
+    def evaluate(self, num_eps: int, model_eps: str = "latest", max_episode_steps=None) -> Tuple[List[float], List[float], List[float], List[float], str]:
+        """Returns (success rates, efficiency scores, effort scores, rewards, 'GTSP') of `num_eps` finished episodes, with action_type 'velocity' and
+        sim.t_max = `t_max`.
+        num_envs == 1: the reference's loop on the reference-shaped single env -- plan where an episode begins, steer, step, and feed the host
+        ``TaskDrivenMetric``, one episode after another (`max_episode_steps` is not used).
+        num_envs > 1: the policy's `num_envs` envs side by side, every finished env starting its next episode at once, until at least `num_eps` episodes
+        have finished; the four lists come from the on-device episode metrics (``episode_metrics()``, the same TaskDrivenMetric), in the order the
+        episodes finished (env order within a step).  An episode ends when the env terminates or truncates, or after `max_episode_steps` steps
+        (None: no limit beside sim.t_max); the reset that follows closes it as truncated.
+        Planner, controller and simulation run on the device either way."""
+        if self.num_envs > 1:
+            return self._evaluate_batched(num_eps, max_episode_steps)
         from ....envs.area_clearing import AreaClearingEnv
         from ....metrics.task_driven_metric import TaskDrivenMetric
         env = AreaClearingEnv(cfg=self._velocity_cfg(), **self.env_kwargs)
@@ -96,6 +105,31 @@ class PlanningBasedPolicy(BasePolicy):
             env.close()
             self._wipe()
         return metric.success_rates, metric.efficiency_scores, metric.effort_scores, metric.rewards, "GTSP"
+
+    def _evaluate_batched(self, num_eps, max_episode_steps):
+        import torch
+        env = self._ensure_env()
+        env.reset()
+        self._wipe()
+        age = torch.zeros(env.num_envs, dtype=torch.int64, device=env.device)
+        success, eff, effort, rewards = [], [], [], []
+        fresh = None
+        while len(eff) < num_eps:
+            _, _, term, trunc, _ = env.step(self.act_batch(env, fresh))
+            age += 1
+            done = term.bool() | trunc.bool()
+            if max_episode_steps is not None:
+                done = done | (age >= int(max_episode_steps))
+            fresh = None
+            if bool(done.any()):
+                env.reset(done)                       # a reset of a running episode closes it as truncated
+                rows, _ = env.episode_metrics()
+                for r in rows[done].cpu().numpy():
+                    eff.append(float(r[0])), effort.append(float(r[1])), rewards.append(float(r[2])), success.append(float(r[3]))
+                age = torch.where(done, torch.zeros_like(age), age)
+                fresh = done
+        env.check_errors()
+        return success, eff, effort, rewards, "GTSP"
 
     # -- the reference's single-env surface ------------------------------------------------------------------
     def update_boundary_and_obstacles(self, boundary, walls, static_obstacles):

@@ -41,6 +41,7 @@ struct BdParams {
     // (busy envs only, budget 0); the tail kernels run with sel_want 0.
     int budget, pass, sel_want;
     int resume_sel;                     // second pass: 0 = every unfinished env, 1 = those that stopped inside execute_robot_path, 2 = the others (until-still loop)
+    double robot_mass;                  // agent.mass: m0 of TaskDrivenMetric (k_task_metrics)
     int cycle_skip;                     // > 0: the second pass of the two-pass step looks for exact recurrences of the robot's state in execute_robot_path once a path has run this many sim steps, and skips whole periods (bd_physics_body<DAMP, CYC>; BP_BD_CYCLE=0 turns it off)
 };
 struct BdPtrs {
@@ -77,6 +78,7 @@ struct BdPtrs {
     float *rmap;                    // [E][SH*SW] spfa map from the robot (observation channel 2)  [record: bp_observe reads it]
     const d2 *goals;                // [ngoal] area-clearing goal points
     unsigned char *cleared;         // [E][BD_MAXBOX] area-clearing box_clearance_statuses  [record]
+    double *m_box;                  // [E][BD_MAXBOX][3] area, cx, cy of every box polygon as it stood after the reset (zeros in unused slots): TaskDrivenMetric's snapshot (k_task_metrics)  [record]
 };
 
 // ---- deterministic libm replacements (fdlibm s_atan.c / e_atan2.c restated, fixed operation order, no FMA contraction) --------
@@ -1195,6 +1197,7 @@ __global__ __launch_bounds__(64) void k_bd_finish(const DevParams P, const DevPt
         if (inactivity >= B.inactivity_cutoff) { term = 1; trunc = 1; }
         Q.cum[env * 4 + 0] = cumd; Q.cum[env * 4 + 1] = cumr; Q.cnt[env * 4 + 0] = inactivity; Q.cnt[env * 4 + 1] = cumb;
         D.e_total_work[env] = tw;
+        D.e_lastrew[env] = robot_reward; D.e_lastflag[env] = term | (trunc << 1);   // what k_task_metrics accounts for this step
         Q.nalive[env] = nalive; Q.nprev[env] = nalive;
         if (reward) reward[env] = robot_reward;
         if (terminated) terminated[env] = (unsigned char)term;
@@ -1333,6 +1336,7 @@ __global__ __launch_bounds__(64) void k_ac_finish(const DevParams P, const DevPt
         } else {
             const double tw = D.e_total_work[env] + work;
             D.e_total_work[env] = tw;
+            D.e_lastrew[env] = rwd; D.e_lastflag[env] = term | (trunc << 1);   // what k_task_metrics accounts for this step
             Q.cnt[env * 4 + 2] = num_completed; Q.cnt[env * 4 + 3] = tcount;
             sf[4] = 0.0; // self.robot_hit_obstacle = False at the end of step (area_clearing.py:776)
             if (reward) reward[env] = rwd;

@@ -866,6 +866,8 @@ __global__ __launch_bounds__(256) void k_episode_metrics(const DevParams P, cons
     }
 }
 
+#include "bp_taskmetric.hpp"   // k_task_metrics: the same for box-delivery / area-clearing handles (needs bp_round2)
+
 enum { MODE_ASYNC = 2, MODE_DRAIN = 3 };   // box-delivery / area-clearing: bp_bd_step_async, bp_bd_async_drain
 struct AsyncArgs {                         // what those two calls hand to launch() beside the step's outputs
     int budget;                            // sim steps per env and call (0: no limit, the drain)
@@ -981,6 +983,9 @@ static int launch(bp_handle *h, int mode, const double *actions, const unsigned 
                 HIPCHK(h, hipGetLastError());
                 HIPCHK(h, hipStreamWaitEvent(st, h->ev_join, 0));
                 }
+                // episode metrics of the step (TaskDrivenMetric): both groups' finish kernels have joined the caller's stream
+                hipLaunchKernelGGL(k_task_metrics, dim3((E + 255) / 256), dim3(256), 0, st, h->P, h->B, h->D, h->Q, 0, (const unsigned char *)nullptr, (const unsigned char *)nullptr);
+                HIPCHK(h, hipGetLastError());
             } else if (mode == MODE_ASYNC || mode == MODE_DRAIN) {
                 // Asynchronous step (bp_bd_step_async / bp_bd_async_drain, DESIGN.md "Asynchronous step"): idle envs are planned and started, busy ones resumed, each
                 // runs at most `as->budget` sim steps; the envs whose env step ended (group byte 0) go through the tail kernels exactly as in the one-pass step.
@@ -1011,6 +1016,9 @@ static int launch(bp_handle *h, int mode, const double *actions, const unsigned 
                 else hipLaunchKernelGGL(k_bd_finish, dim3(E), dim3(64), h->bd_lds, st, h->P, h->D, Bt, h->Q, 0, 0, reward, term, trunc, info);
                 HIPCHK(h, hipGetLastError());
                 HIPCHK(h, hipStreamWaitEvent(st, h->ev_join, 0));
+                // episode metrics: only the envs that emitted a transition in this call are accounted
+                hipLaunchKernelGGL(k_task_metrics, dim3((E + 255) / 256), dim3(256), 0, st, h->P, h->B, h->D, h->Q, 0, (const unsigned char *)nullptr, (const unsigned char *)as->ready);
+                HIPCHK(h, hipGetLastError());
                 if (raster && obs) {
                     hipLaunchKernelGGL(k_bd_observe, dim3(E), dim3(BDO_THREADS), h->bd_obs_lds, st, h->P, h->D, Bt, h->Q, (const unsigned char *)nullptr, obs);
                     HIPCHK(h, hipGetLastError());
@@ -1020,6 +1028,9 @@ static int launch(bp_handle *h, int mode, const double *actions, const unsigned 
                 hipLaunchKernelGGL(k_reset_copy, dim3(E), dim3(256), 0, st, h->P, h->D, mask, (double *)nullptr);
                 HIPCHK(h, hipGetLastError());
                 hipLaunchKernelGGL(k_bd_reset_copy, dim3(E), dim3(256), 0, st, h->P, h->D, h->B, h->Q, mask, info);
+                HIPCHK(h, hipGetLastError());
+                // closes the running episodes of the mask and takes the new episode's snapshot (start position, box areas / centroids) from the reset state
+                hipLaunchKernelGGL(k_task_metrics, dim3((E + 255) / 256), dim3(256), 0, st, h->P, h->B, h->D, h->Q, 1, mask, (const unsigned char *)nullptr);
                 HIPCHK(h, hipGetLastError());
             }
         }
@@ -1333,8 +1344,6 @@ int bp_get_episode_metrics(bp_handle *h, double *rows, uint32_t *counts, void *s
 {
     if (!h) return BP_EINVAL;
     if (!h->loaded) return fail(h, BP_ESTATE, "not loaded");
-    if (h->P.env_kind != BP_ENV_SHIP_ICE && h->P.env_kind != BP_ENV_MAZE)
-        return fail(h, BP_EINVAL, "episode metrics are kept for ship-ice and maze handles only");
     BP_DEVICE(h);
     if (rows) HIPCHK(h, hipMemcpyAsync(rows, h->D.m_rows, sizeof(double) * BP_EPM_COUNT * h->num_envs, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     if (counts) HIPCHK(h, hipMemcpyAsync(counts, h->D.m_count, sizeof(unsigned) * h->num_envs, hipMemcpyDeviceToDevice, (hipStream_t)stream));
@@ -1345,14 +1354,43 @@ int bp_get_episode_history(bp_handle *h, double *ring, double *sums, uint32_t *c
 {
     if (!h) return BP_EINVAL;
     if (!h->loaded) return fail(h, BP_ESTATE, "not loaded");
-    if (h->P.env_kind != BP_ENV_SHIP_ICE && h->P.env_kind != BP_ENV_MAZE)
-        return fail(h, BP_EINVAL, "episode metrics are kept for ship-ice and maze handles only");
     BP_DEVICE(h);
     const size_t E = (size_t)h->num_envs;
     if (ring) HIPCHK(h, hipMemcpyAsync(ring, h->D.m_ring, sizeof(double) * BP_EPM_RING * BP_EPM_COUNT * E, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     if (sums) HIPCHK(h, hipMemcpyAsync(sums, h->D.m_sum, sizeof(double) * BP_EPM_COUNT * E, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     if (counts) HIPCHK(h, hipMemcpyAsync(counts, h->D.m_count, sizeof(unsigned) * E, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return BP_OK;
+}
+
+int bp_bd_get_episode_boxes(bp_handle *h, double *out, void *stream)
+{
+    if (!h || !out) return BP_EINVAL;
+    if (!h->loaded) return fail(h, BP_ESTATE, "not loaded");
+    if (h->P.env_kind != BP_ENV_BOX) return fail(h, BP_EINVAL, "bp_bd_get_episode_boxes: not a box-delivery / area-clearing handle");
+    BP_DEVICE(h);
+    HIPCHK(h, hipMemcpyAsync(out, h->Q.m_box, sizeof(double) * BD_MAXBOX * 3 * (size_t)h->num_envs, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return BP_OK;
+}
+
+int bp_bd_get_completed(bp_handle *h, uint8_t *out_host)
+{
+    if (!h || !out_host) return BP_EINVAL;
+    if (!h->loaded || h->P.env_kind != BP_ENV_BOX) return fail(h, BP_EINVAL, "bp_bd_get_completed: not a loaded box-delivery / area-clearing handle");
+    BP_DEVICE(h);
+    HIPCHK(h, hipDeviceSynchronize());
+    const size_t n = (size_t)h->num_envs * BD_MAXBOX;
+    HIPCHK(h, hipMemcpy(out_host, h->B.task == 1 ? h->Q.cleared : h->Q.alive, n, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; i++) out_host[i] = (uint8_t)((int)(i % BD_MAXBOX) < h->B.nbox && (out_host[i] != 0) == (h->B.task == 1));
+    return BP_OK;
+}
+
+// host only: the arithmetic of k_task_metrics' emit path (bp_taskmetric.hpp) on caller-supplied data
+int bp_task_metric_row(int32_t nbox, const double *boxes_acxy, const uint8_t *completed, int32_t ngoal, const double *goals_xy, const double *start_xy,
+                       double robot_mass, double robot_dist, double total_work, double reward, double steps, double *out6)
+{
+    if (!boxes_acxy || !completed || !goals_xy || !start_xy || !out6 || nbox < 0 || nbox > BD_MAXBOX || ngoal < 1) return -1;
+    tm_row(nbox, boxes_acxy, completed, ngoal, goals_xy, start_xy[0], start_xy[1], robot_mass, robot_dist, total_work, reward, steps, out6);
+    return 0;
 }
 
 // test hook: every written hint word of the live envs gets random VALID contents -- plane and support-vertex indices below the vertex counts the word
@@ -1784,6 +1822,7 @@ int bp_bd_create(const bp_bd_config *cfg, int32_t num_envs, int64_t env_id_offse
     B.local_px = cfg->local_px; B.use_correct_direction_reward = cfg->use_correct_direction_reward;
     B.inactivity_cutoff = cfg->inactivity_cutoff; B.num_boxes = cfg->num_boxes; B.step_limit = cfg->step_limit;
     B.first_box = 6;
+    B.robot_mass = cfg->robot_mass;
     B.action_type = cfg->action_type;
     if (cfg->action_type < 0 || cfg->action_type > 2) { delete h; return BP_EINVAL; }
     B.task = cfg->task; B.omega_scale = cfg->omega_scale; B.v_scale = cfg->v_scale; B.lfc = cfg->lfc;
@@ -1974,6 +2013,7 @@ int bp_bd_load(bp_handle *h, int32_t T, int32_t nbox, const double *starts, cons
     if ((rc = dalloc(h, &Q.dist, E * NW))) return rc;
     if ((rc = dalloc(h, &Q.rmap, E * NW))) return rc;
     if ((rc = dalloc(h, &Q.cleared, E * BD_MAXBOX))) return rc;
+    if ((rc = dalloc(h, &Q.m_box, E * BD_MAXBOX * 3))) return rc;
     {
         d2 *d_goals;
         if ((rc = dalloc(h, &d_goals, 128))) return rc;

@@ -119,6 +119,8 @@ struct DevPtrs {
     double *e_lastrew;       // [E]
     int *e_lastflag;         // [E] bit0 terminated, bit1 trial_success
     double *m_acc;           // [E][8] episode reward, path length l0, previous rounded x, y, L, steps, total_work, success
+                             //        box-delivery / area-clearing handles (k_task_metrics): [4] and [7] hold the rounded start x and y instead (L has no meaning there,
+                             //        success is computed when the row is emitted); e_lastflag there: bit 0 terminated, bit 1 truncated, bits 8..31 completed box k of the last step
     double *m_rows;          // [E][BP_EPM_COUNT] most recently finished episode
     double *m_ring;          // [E][BP_EPM_RING][BP_EPM_COUNT] the last BP_EPM_RING finished episodes (episode n in slot n % BP_EPM_RING)
     double *m_sum;           // [E][BP_EPM_COUNT] row fields summed over all finished episodes

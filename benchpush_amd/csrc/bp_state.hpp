@@ -88,7 +88,7 @@ inline BpStateLayout bp_state_layout(const DevPtrs &D, const BdPtrs &Q, int nbca
         BP_SEG_Q(alive, BD_MAXBOX); BP_SEG_Q(order, BD_MAXBOX); BP_SEG_Q(nalive, 1); BP_SEG_Q(nprev, 1);
         BP_SEG_Q(boxdist, BD_MAXBOX); BP_SEG_Q(boxpos, BD_MAXBOX); BP_SEG_Q(prev, BD_MAXBOX * 4);
         BP_SEG_Q(cum, 4); BP_SEG_Q(cnt, 4); BP_SEG_Q(wp, BD_MAXWP * 3); BP_SEG_Q(nwp, 1); BP_SEG_Q(stepf, 8);
-        BP_SEG_Q(cleared, BD_MAXBOX);
+        BP_SEG_Q(cleared, BD_MAXBOX); BP_SEG_Q(m_box, BD_MAXBOX * 3);
         BP_SEG_Q(rmap, map_cells);   // observation channel 2 is read from it: bp_observe straight after a load must give the saved observation
     }
 #undef BP_SEG_D

@@ -162,6 +162,21 @@ class BatchedBoxDeliveryEnv(BatchedShipIceEnv):
                                                         p(out["small_free"])), "bp_bd_get_maps")
         return out
 
+    def episode_boxes(self):
+        """float64 [E, 24, 3] on the device: (area, cx, cy) of every box polygon as it stood after the env's last reset, zeros in unused slots -- the snapshot
+        the episode metrics (``episode_metrics()``, ``episode_history()``, ``episode_lists()``: the reference's TaskDrivenMetric) take the boxes' goal
+        distances and the spanning tree from."""
+        out = torch.zeros((self.num_envs, _lib.BD_MAXBOX, 3), dtype=torch.float64, device=self.device)
+        _lib.check(self.L, self.h, self.L.bp_bd_get_episode_boxes(self.h, _ptr(out), self._stream()), "bp_bd_get_episode_boxes")
+        return out
+
+    def box_completed(self):
+        """uint8 [E, 24] (host copy): info['box_completed_statuses'] of every env -- box k delivered (box-delivery) / cleared (area-clearing) after the last
+        step; what the episode metrics count as completed."""
+        out = np.zeros((self.num_envs, _lib.BD_MAXBOX), np.uint8)
+        _lib.check(self.L, self.h, self.L.bp_bd_get_completed(self.h, out.ctypes.data_as(C.c_void_p)), "bp_bd_get_completed")
+        return out
+
     def box_state(self):
         """(alive uint8 [E, 24], waypoints [E, 64, 3], number of waypoints [E]) of the last step (host copies).  While an asynchronous slice is open a
         busy env shows the waypoints of the env step it is in, and the alive flags from before that step."""

@@ -514,7 +514,8 @@ class BatchedShipIceEnv(_BatchedBase):
         return actions, ct_err, diag
 
     def episode_metrics(self):
-        """On-device ShipIceMetric: (rows [E, 6] float64 = efficiency, effort, episode reward, success, episode length, total_work of
+        """On-device ShipIceMetric (maze: MazeNamoMetric; box-delivery / area-clearing: TaskDrivenMetric, where success is the rate of completed boxes and
+        0 / 0, x / 0 give NaN / inf like the host class): (rows [E, 6] float64 = efficiency, effort, episode reward, success, episode length, total_work of
         each env's most recently finished episode; counts [E] int32 = episodes finished so far).  Device tensors; rows of envs with
         count 0 are zero.  This is the block benchpush_amd.parallel.allgather_episode_metrics carries between GPUs."""
         rows = torch.zeros((self.num_envs, 6), dtype=torch.float64, device=self.device)

@@ -206,6 +206,16 @@ class BatchedVecEnv(_Base):
             self._steps[idx] = state.extra["vec_steps"].to(dv)
             self._term_obs[idx] = state.extra["vec_term_obs"].to(dv)
 
+    # -- the on-device episode metrics of the wrapped env, all four environments ----------------------------
+    def episode_metrics(self):
+        return self.env.episode_metrics()
+
+    def episode_history(self):
+        return self.env.episode_history()
+
+    def episode_lists(self):
+        return self.env.episode_lists()
+
     def step(self, actions):
         self.step_async(actions)
         return self.step_wait()

@@ -1,4 +1,4 @@
-"""TaskDrivenMetric for area-clearing (reference: benchpush/common/metrics/task_driven_metric.py:8-155).
+"""TaskDrivenMetric for box-delivery and area-clearing (reference: benchpush/common/metrics/task_driven_metric.py:8-155).
 
 efficiency = MST cost over {robot start, cleared boxes, each box's nearest goal point} / robot path length (plus the success rate),
 effort = (m0 l0 + sum_i min-goal-distance_i * area_i) / (m0 l0 + total_work).  The reference builds shapely Polygons and a networkx
@@ -18,6 +18,14 @@ def _area_centroid(poly):
     a = cr.sum() / 2
     cx, cy = ((x + xn) * cr).sum() / (6 * a), ((y + yn) * cr).sum() / (6 * a)
     return abs(a), (cx, cy)
+
+
+def _dist(a, b):
+    """Euclidean distance of two points as sqrt(dx * dx + dy * dy) in float64, one rounding per operation.  (np.linalg.norm goes through the BLAS dot
+    product, which fuses the multiply-add on some builds and not on others; the on-device metric -- csrc/bp_taskmetric.hpp -- and this class must give the
+    same bits everywhere.)"""
+    dx, dy = np.float64(a[0]) - np.float64(b[0]), np.float64(a[1]) - np.float64(b[1])
+    return np.sqrt(dx * dx + dy * dy)
 
 
 def _mst_weight(n, edges):
@@ -66,9 +74,9 @@ class TaskDrivenMetric(BaseMetric):
         edges = []
         for i in range(k):
             for j in range(i + 1, k):
-                edges.append((i, j, float(np.linalg.norm(np.array(done[i]) - np.array(done[j])))))
-            edges.append((robot, i, float(np.linalg.norm(np.array(self.initial_robot_state[:2]) - np.array(done[i])))))
-            edges.append((i, i + k, min(float(np.linalg.norm(np.array(done[i]) - np.array(g))) for g in self.goal_positions)))
+                edges.append((i, j, float(_dist(done[i], done[j]))))
+            edges.append((robot, i, float(_dist(self.initial_robot_state, done[i]))))
+            edges.append((i, i + k, min(float(_dist(done[i], g)) for g in self.goal_positions)))
         return _mst_weight(2 * k + 1, edges)
 
     def compute_efficiency_score(self, mst_cost):
@@ -80,7 +88,7 @@ class TaskDrivenMetric(BaseMetric):
         for (area, c), s in zip(zip(self._areas, self._centroids), self.box_completed_statuses):
             if not s:
                 continue
-            d = min(float(np.linalg.norm(np.array([g[0], g[1]]) - np.array(c))) for g in self.goal_positions)
+            d = min(float(_dist(g, c)) for g in self.goal_positions)
             min_mass_dist += d * (self.box_mass if self.box_mass is not None else area)
         own = self.robot_mass * self.total_robot_dist
         return (own + min_mass_dist) / (own + self.total_mass_dist)
@@ -90,7 +98,7 @@ class TaskDrivenMetric(BaseMetric):
         self.total_mass_dist = info["total_work"]
         self.box_completed_statuses = info["box_completed_statuses"]
         cur = info["state"]
-        self.total_robot_dist += np.linalg.norm(np.array(self.robot_state[:2]) - np.array(cur[:2]))
+        self.total_robot_dist += _dist(self.robot_state, cur)
         self.robot_state = cur
         if eps_complete:
             self.rewards.append(self.eps_reward)

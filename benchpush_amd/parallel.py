@@ -31,7 +31,7 @@ def allgather_episode_metrics(local, dist=None):
 
 
 def gather_episode_block(rows, counts, dist=None):
-    """The per-rank [E/R, 6] episode rows of BatchedShipIceEnv.episode_metrics() (efficiency, effort, reward, success, length,
+    """The per-rank [E/R, 6] episode rows of episode_metrics() of any of the four batched envs -- ship-ice, maze, box-delivery, area-clearing -- (efficiency, effort, reward, success, length,
     total_work of every env's last finished episode) plus the finished-episode counts -> the whole job's ([E, 6], [E]) in global env
     order (ranks own contiguous env ranges, so rank-major order is env order).  One all-gather of a fixed [E/R, 7] float64 block:
     4096 envs per GPU = 229 KB per rank, once per evaluation batch."""
@@ -41,7 +41,7 @@ def gather_episode_block(rows, counts, dist=None):
 
 
 def gather_episode_sums(sums, counts, dist=None):
-    """The per-rank [E/R, 6] sums over ALL finished episodes of every env (BatchedShipIceEnv.episode_history()) plus the episode counts -> the whole
+    """The per-rank [E/R, 6] sums over ALL finished episodes of every env (episode_history() of any of the four batched envs: ship-ice, maze, box-delivery, area-clearing) plus the episode counts -> the whole
     job's ([E, 6], [E]) in global env order: one all-gather of a fixed [E/R, 7] float64 block per evaluation, whatever the number of episodes."""
     block = torch.cat([sums.to(torch.float64), counts.to(torch.float64).reshape(-1, 1)], dim=1)
     allb = allgather_episode_metrics(block, dist)

@@ -188,7 +188,7 @@ int bp_get_body_state(bp_handle *h, double *out, void *stream);
 /* low-dimensional observation (ship_ice_env.py:358-370): |centroid| of every floe, device double [E][nb_cap-1][2] */
 int bp_get_low_dim_obs(bp_handle *h, double *out, void *stream);
 
-/* Per-episode metrics accumulated on the device (ship-ice and maze handles; the maze uses MazeNamoMetric's L = wavefront length at the
+/* Per-episode metrics accumulated on the device (all four environments; box-delivery and area-clearing handles: see below; the maze uses MazeNamoMetric's L = wavefront length at the
  * start pixel, maze_namo_metric.py:68-75, and bp_config.ship_mass = cfg.robot.mass): what ShipIceMetric.update / reset keep per episode
  * (benchpush/common/metrics/ship_ice_metric.py:26-69, base_metric.py:12-16) -- summed reward, path length of the ship integrated from
  * the state rounded to 2 decimals like info['state'] (ship_ice_env.py:337-339), total_work, success, steps -- updated by every bp_step /
@@ -208,6 +208,23 @@ int bp_get_episode_metrics(bp_handle *h, double *rows, uint32_t *counts, void *s
  *   counts device uint32 [E] episodes finished so far.  Any pointer may be NULL. */
 #define BP_EPM_RING 8
 int bp_get_episode_history(bp_handle *h, double *ring, double *sums, uint32_t *counts, void *stream);
+/* Box-delivery and area-clearing handles keep the reference's TaskDrivenMetric (benchpush/common/metrics/task_driven_metric.py) in the same rows, updated
+ * by bp_step / bp_reset / bp_bd_step_async / bp_bd_async_drain (an asynchronous call accounts only the envs whose ready byte it set):
+ *   efficiency = mst_cost / l0, effort = (m0 l0 + sum_i d_i area_i) / (m0 l0 + total_work) over the completed boxes i, episode reward,
+ *   success = completed boxes / boxes (a rate), steps, total_work -- l0 the path length of the robot position rounded to 2 decimals, m0 =
+ *   bp_bd_config.robot_mass, d_i the distance from box i's centroid AT RESET to the nearest goal (receptacle position / boundary goal points), mst_cost the
+ *   minimum spanning tree over the completed boxes' reset centroids, their goals and the robot start.  0 / 0 and x / 0 are IEEE (NaN, inf).
+ * bp_bd_get_episode_boxes: device double [E][24][3] = area, cx, cy of every box polygon as it stood after the env's last reset (zeros in unused slots);
+ * BP_EINVAL for handles of the other environments. */
+int bp_bd_get_episode_boxes(bp_handle *h, double *out_device, void *stream);
+/* info['box_completed_statuses'] of every env as the metric reads it: host uint8 [E][24], 1 = box k is delivered (box-delivery: no longer alive) / cleared
+ * (area-clearing), 0 otherwise and in unused slots (synchronises).  BP_EINVAL for handles of the other environments. */
+int bp_bd_get_completed(bp_handle *h, uint8_t *out_host);
+/* The row arithmetic of those handles as a pure host function (no GPU, no handle; the code the kernel runs): boxes_acxy [nbox][3] = area, cx, cy;
+ * completed uint8 [nbox]; goals_xy [ngoal][2]; start_xy [2]; robot_dist = l0; out6 = the BP_EPM_* columns.  Returns 0, or -1 for a null pointer, nbox outside
+ * 0 .. 24 or ngoal < 1. */
+int bp_task_metric_row(int32_t nbox, const double *boxes_acxy, const uint8_t *completed, int32_t ngoal, const double *goals_xy, const double *start_xy,
+                       double robot_mass, double robot_dist, double total_work, double reward, double steps, double *out6);
 /* Rollout plumbing for vectorised callers (the reference's learners wrap the env in SB3's VecEnv, whose auto-reset hands the LAST observation of a
  * finished episode back as infos[i]['terminal_observation'], baselines/ship_ice_nav/ppo/policy.py:29-69): copies row r of src to row r of dst for every r with
  * mask[r] != 0 -- device pointers, rows of row_bytes bytes (a multiple of 4), nothing is read back, so the caller can save the observations of the envs that are
@@ -323,6 +340,7 @@ typedef struct bp_bd_config {
     double robot_verts[4][2];          /* agent.vertices */
     double wheel_verts[4][4][2];       /* agent.wheel_vertices */
     double bumper_verts[4][2];         /* agent.front_bumper_vertices */
+    double robot_mass;                 /* agent.mass: m0 of the episode metrics (TaskDrivenMetric); last member, added within ABI 11 */
 } bp_bd_config;
 /* area-clearing-v0 uses the same entry points with bp_bd_config.task = 1: heading/position/velocity actions, obs uint8
  * [E][224][224][4], info columns = x, y, theta, total_work, collision reward, diff_reward, box_completed_reward, box_count, ministeps,
