@@ -34,7 +34,8 @@ EXPORTS = ["bp_abi_version", "bp_create", "bp_destroy", "bp_load_scenarios", "bp
            "bp_sizeof_track_config", "bp_track_path",
            "bp_sizeof_rrt_config", "bp_rrt_workspace_bytes", "bp_rrt_uniform", "bp_rrt_plan", "bp_sizeof_track_wp_config", "bp_track_waypoints",
            "bp_sizeof_gtsp_config", "bp_gtsp_workspace_bytes", "bp_gtsp_plan", "bp_gtsp_track",
-           "bp_bd_step_async", "bp_bd_async_drain", "bp_bd_async_open", "bp_bd_get_episode_boxes", "bp_bd_get_completed", "bp_task_metric_row"]
+           "bp_bd_step_async", "bp_bd_async_drain", "bp_bd_async_open", "bp_bd_get_episode_boxes", "bp_bd_get_completed", "bp_task_metric_row",
+           "bp_bd_queue_open", "bp_bd_queue_recv", "bp_bd_queue_send", "bp_bd_queue_close", "bp_bd_queue_batch"]
 GTSP_OK, GTSP_NOTHING_TO_PUSH, GTSP_SKIPPED, GTSP_CAP, GTSP_INVALID = range(5)
 GTSP_STATUS_MASK, GTSP_FLAG_VANISHED, GTSP_FLAG_DEGENERATE = 0xFF, 0x100, 0x200   # status = code | flags
 GTSP_MAX_BOXES, GTSP_MAX_GOALS, GTSP_MAX_SLOTS = 12, 8, 64
@@ -45,6 +46,7 @@ LATTICE_FOUND, LATTICE_NO_PATH, LATTICE_CAP, LATTICE_SKIPPED = 0, 1, 2, 3
 LATTICE_MAX_EDGES = 32   # bp_lattice_search: edges per base heading at most
 SWATH_CLIP, SWATH_REJECT = 0, 1
 SWATH_MAX_WORDS = 4096   # bp_swath_cost: H * ceil(W / 64) at most (the swath's bit image lives in LDS)
+QUEUE_FULL_ONLY = 1   # BP_QUEUE_FULL_ONLY: bp_bd_queue_recv takes nothing while fewer than M ids are queued and an env is still busy
 STATE_TRUSTED = 1    # BP_STATE_TRUSTED: bp_load_state / bp_clone_state skip the argument checks and the synchronisation
 
 
@@ -204,6 +206,13 @@ def load():
         L.bp_bd_async_drain.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.bp_bd_async_open.argtypes = [vp]
         L.bp_bd_async_open.restype = C.c_int32
+    if hasattr(L, "bp_bd_queue_open"):   # ready queue of the asynchronous step (absent from older builds loaded for same-box comparisons)
+        L.bp_bd_queue_open.argtypes = [vp, C.c_int32, vp]
+        L.bp_bd_queue_recv.argtypes = [vp, C.c_int32, C.c_int32] + [vp] * 16
+        L.bp_bd_queue_send.argtypes = [vp] * 7
+        L.bp_bd_queue_close.argtypes = [vp] * 9
+        L.bp_bd_queue_batch.argtypes = [vp]
+        L.bp_bd_queue_batch.restype = C.c_int32
     if hasattr(L, "bp_task_metric_row"):   # episode metrics of box handles (absent from older builds loaded for same-box comparisons)
         L.bp_bd_get_episode_boxes.argtypes = [vp, vp, vp]
         L.bp_bd_get_completed.argtypes = [vp, vp]

@@ -68,7 +68,7 @@ struct BdPtrs {
     int *nwp;                       // [E]  [record]
     double *stepf;                  // [E][8] robot_distance, ix, iy, ih, hit, substeps, -, -  [record]
     unsigned char *unfin;           // [E] 1 = the env's sim-step loop hit the budget of pass 0 (its loop state is in rs_i / rs_d) -- written by pass 0 for every env  [no record: loop state of the two-pass step, as rs_i / rs_d]
-    //                                 asynchronous step (bd_physics_body<.., SLICE>): 1 = busy between calls, 0 = finished in the last call / idle, 2 = idle env of a drain; the lock-step pass 1
+    //                                 asynchronous step (bd_physics_body<.., SLICE>): 1 = busy between calls, 0 = finished in the last call / idle, 2 = idle env of a drain, 3 = held by the ready queue (bp_asyncq.hpp); the lock-step pass 1
     //                                 never clears the byte, so opening a slice clears it (bp_bd_step_async)
     int *rs_i;                      // [E][16] phase, wi, path0, done_turning, dp_valid, sp_one, sim_steps, kcount, have_prev, still_done, total_sub, robot_hit, cycles >> 8, hit_limit,
     //                                 [14] calls of the asynchronous env step so far, [15] serial number of the asynchronous call that last served the env  [no record: loop state, as unfin]
@@ -542,7 +542,8 @@ __global__ __launch_bounds__(64) void k_bd_plan(const DevParams P, const DevPtrs
 __global__ __launch_bounds__(64) void k_bd_plan_async(const DevParams P, const DevPtrs D, const BdParams B, const BdPtrs Q,
                                                       const double *__restrict__ actions)
 {
-    if (Q.unfin[blockIdx.x] == 1) return;
+    const unsigned char group = Q.unfin[blockIdx.x];
+    if (group == 1 || group == 3) return;   // busy, or held by the ready queue (3, bp_asyncq.hpp: the env has no action yet)
     bd_plan_body(P, D, B, Q, actions);
 }
 
@@ -649,6 +650,10 @@ __device__ __forceinline__ void bd_physics_body(const DevParams &P, const DevPtr
     if constexpr (SLICE) {
         int *ri0 = Q.rs_i + (size_t)env * 16;
         if (ri0[15] == epoch) return;                                     // served by the other launch of this call
+        if (Q.unfin[env] == 3) {                                          // held by the ready queue (bp_asyncq.hpp): no transition, the byte stays
+            if (lane_id() == 0) { ready[env] = 0; ri0[15] = epoch; }
+            return;
+        }
         slice_busy = Q.unfin[env] == 1;
         if (B.resume_sel != 0 && (slice_busy ? ((ri0[0] == 0) != (B.resume_sel == 1)) : (B.resume_sel == 1))) return;   // the other launch's env (resume_sel 0: one launch)
         if (!slice_busy && B.pass == 3) {                                 // idle env of a drain: no transition

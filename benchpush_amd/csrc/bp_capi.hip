@@ -26,6 +26,7 @@
 #include "bp_track.hpp"
 #include "bp_rrt.hpp"
 #include "bp_gtsp.hpp"
+#include "bp_asyncq.hpp"
 
 struct bp_handle {
     bp_config cfg;
@@ -61,6 +62,8 @@ struct bp_handle {
     // asynchronous step of box-delivery / area-clearing (bp_bd_step_async / bp_bd_async_drain)
     bool async_open = false;        // a slice is open: envs may be in the middle of an env step (host flag; set by bp_bd_step_async, cleared by the drain and by a reset of all envs)
     int as_epoch = 0;               // serial number of the last asynchronous call (the two launches of a call tell each other's envs apart by it)
+    int q_batch = 0;                // > 0: a ready queue with this batch size is open on the slice (bp_bd_queue_*; host flag, as async_open)
+    BdQueue q = {};                 // its device arrays, allocated by the first bp_bd_queue_open
     DevParams P;
     DevPtrs D;
     std::vector<void *> allocs;
@@ -1175,6 +1178,8 @@ int bp_reset(bp_handle *h, const uint8_t *env_mask, uint8_t *obs, double *info, 
 {
     if (!h) return BP_EINVAL;
     if (!h->loaded) return fail(h, BP_ESTATE, "bp_load_scenarios has not been called");
+    if (h->q_batch > 0 && env_mask != nullptr)
+        return fail(h, BP_ESTATE, "bp_reset with a mask while a ready queue is open: envs are reset through bp_bd_queue_send (bp_bd_queue_close or a reset of all envs closes the queue)");
     BP_DEVICE(h);
     if (h->async_open && env_mask != nullptr) {   // an asynchronous slice is open: the busy envs of the mask are cancelled (a reset of all envs closes the slice instead)
         hipLaunchKernelGGL(k_bd_async_cancel, dim3((h->num_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->Q, env_mask, h->num_envs);
@@ -1185,7 +1190,7 @@ int bp_reset(bp_handle *h, const uint8_t *env_mask, uint8_t *obs, double *info, 
     const int rc = launch(h, MODE_RESET, nullptr, env_mask, obs, nullptr, nullptr, nullptr, info, (hipStream_t)stream, true, true);
     h->timing = save;
     if (rc == BP_OK) h->was_reset = true;
-    if (rc == BP_OK && env_mask == nullptr) h->async_open = false;
+    if (rc == BP_OK && env_mask == nullptr) { h->async_open = false; h->q_batch = 0; }   // (an open ready queue is discarded with the slice)
     return rc;
 }
 
@@ -1224,6 +1229,7 @@ int bp_bd_step_async(bp_handle *h, const double *actions, int32_t budget, uint8_
     if (!h || !actions || !reward || !terminated || !truncated || !info || !ready || !slices) return BP_EINVAL;
     if (int rc = async_ready(h, "bp_bd_step_async")) return rc;
     if (budget < 1) return fail(h, BP_EINVAL, "bp_bd_step_async: budget < 1 sim step");
+    if (h->q_batch > 0) return fail(h, BP_ESTATE, "bp_bd_step_async while a ready queue is open (bp_bd_queue_recv steps the envs; bp_bd_queue_close or a reset of all envs closes it)");
     BP_DEVICE(h);
     if (!h->async_open) {
         // every env is idle.  The lock-step second pass never clears the group byte, and a drain leaves 2 in it: clear on opening
@@ -1245,6 +1251,7 @@ int bp_bd_async_drain(bp_handle *h, uint8_t *obs, double *reward, uint8_t *termi
 {
     if (!h || !reward || !terminated || !truncated || !info || !ready || !slices) return BP_EINVAL;
     if (int rc = async_ready(h, "bp_bd_async_drain")) return rc;
+    if (h->q_batch > 0) return fail(h, BP_ESTATE, "bp_bd_async_drain while a ready queue is open (bp_bd_queue_close drains and closes it)");
     BP_DEVICE(h);
     if (!h->async_open) {   // no env is busy: nothing to finish
         HIPCHK(h, hipMemsetAsync(ready, 0, (size_t)h->num_envs, (hipStream_t)stream));
@@ -1257,6 +1264,124 @@ int bp_bd_async_drain(bp_handle *h, uint8_t *obs, double *reward, uint8_t *termi
 }
 
 int32_t bp_bd_async_open(bp_handle *h) { return (h && h->async_open) ? 1 : 0; }
+
+// ---- ready queue of the asynchronous step (bp_asyncq.hpp; DESIGN.md "Asynchronous step") ----
+static int queue_ready(bp_handle *h, const char *what)
+{
+    if (int rc = async_ready(h, what)) return rc;
+    if (h->q_batch < 1) return fail(h, BP_ESTATE, std::string(what) + ": no ready queue is open (bp_bd_queue_open)");
+    return BP_OK;
+}
+static int queue_action_dim(const bp_handle *h) { return h->B.action_type == 2 ? 2 : 1; }
+
+int bp_bd_queue_open(bp_handle *h, int32_t batch, void *stream)
+{
+    if (!h) return BP_EINVAL;
+    if (int rc = async_ready(h, "bp_bd_queue_open")) return rc;
+    if (h->async_open) return fail(h, BP_ESTATE, "bp_bd_queue_open while an asynchronous slice is open (bp_bd_async_drain, bp_bd_queue_close or a reset of all envs closes it)");
+    const int E = h->num_envs;
+    if (batch < 1 || batch > E) return fail(h, BP_EINVAL, "bp_bd_queue_open: batch outside [1, num_envs]");
+    BP_DEVICE(h);
+    hipStream_t st = (hipStream_t)stream;
+    if (h->q.ring == nullptr) {
+        BdQueue q = {};
+        int rc;
+        if ((rc = dalloc(h, &q.hdr, (size_t)4))) return rc;
+        if ((rc = dalloc(h, &q.where, (size_t)E))) return rc;
+        if ((rc = dalloc(h, &q.fresh, (size_t)E))) return rc;
+        if ((rc = dalloc(h, &q.rmask, (size_t)E))) return rc;
+        if ((rc = dalloc(h, &q.win, (size_t)E))) return rc;
+        if ((rc = dalloc(h, &q.actions, (size_t)E * 2))) return rc;
+        if ((rc = dalloc(h, &q.ring, (size_t)E))) return rc;   // last: the queue is allocated once all of it is
+        h->q = q;
+    }
+    HIPCHK(h, hipMemsetAsync(h->q.hdr, 0, sizeof(int) * 4, st));
+    HIPCHK(h, hipMemsetAsync(h->q.where, 0, (size_t)E, st));
+    HIPCHK(h, hipMemsetAsync(h->q.actions, 0, sizeof(double) * 2 * (size_t)E, st));
+    if (h->as_epoch > 0x7FFF0000) {   // (serial numbers start over long before they wrap, as in bp_bd_step_async)
+        HIPCHK(h, hipMemsetAsync(h->Q.rs_i, 0, sizeof(int) * 16 * (size_t)E, st));
+        h->as_epoch = 0;
+    }
+    // open before anything is enqueued (as bp_bd_step_async): should a launch fail, the handle refuses bp_step / bp_save_state until a reset of all envs
+    h->async_open = true;
+    h->q_batch = batch;
+    // every env becomes held and is queued with its current (reset) observation as a fresh row, in env-id order
+    hipLaunchKernelGGL(k_bdq_enqueue, dim3(1), dim3(BDQ_THREADS), 0, st, h->q, h->Q.unfin, (const unsigned char *)nullptr, E, 1);
+    HIPCHK(h, hipGetLastError());
+    return BP_OK;
+}
+
+int bp_bd_queue_recv(bp_handle *h, int32_t budget, int32_t flags, uint8_t *obs_e, double *reward_e, uint8_t *terminated_e, uint8_t *truncated_e, double *info_e,
+                     uint8_t *emitted, int32_t *slices_e, int32_t *ids, uint8_t *obs, double *reward, uint8_t *terminated, uint8_t *truncated,
+                     double *info, int32_t *slices, int32_t *counts, void *stream)
+{
+    if (!h || !reward_e || !terminated_e || !truncated_e || !info_e || !emitted || !slices_e || !ids || !reward || !terminated || !truncated || !info ||
+        !slices || !counts)
+        return BP_EINVAL;
+    if (int rc = queue_ready(h, "bp_bd_queue_recv")) return rc;
+    if (budget < 1) return fail(h, BP_EINVAL, "bp_bd_queue_recv: budget < 1 sim step");
+    if ((obs == nullptr) != (obs_e == nullptr)) return fail(h, BP_EINVAL, "bp_bd_queue_recv: obs_e and obs must both be given or both be NULL");
+    const size_t row = (size_t)h->B.local_px * h->B.local_px * 4;
+    if (obs && (row % 16 != 0 || ((uintptr_t)obs_e | (uintptr_t)obs) % 16 != 0))
+        return fail(h, BP_EINVAL, "bp_bd_queue_recv: observation rows must be multiples of 16 bytes in 16-byte aligned tensors");
+    BP_DEVICE(h);
+    hipStream_t st = (hipStream_t)stream;
+    const int E = h->num_envs, M = h->q_batch;
+    // 1. one slice call exactly as bp_bd_step_async launches it; the envs take their actions from the queue's action rows (bp_bd_queue_send wrote them)
+    const AsyncArgs as = {budget, emitted, slices_e};
+    if (int rc = launch(h, MODE_ASYNC, h->q.actions, nullptr, obs_e, reward_e, terminated_e, truncated_e, info_e, st, true, true, &as)) return rc;
+    // 2. the envs that emitted are appended in ascending env id and become held; 3. up to M ids leave the head; 4. their rows are gathered
+    hipLaunchKernelGGL(k_bdq_enqueue, dim3(1), dim3(BDQ_THREADS), 0, st, h->q, h->Q.unfin, (const unsigned char *)emitted, E, 0);
+    HIPCHK(h, hipGetLastError());
+    hipLaunchKernelGGL(k_bdq_take, dim3(1), dim3(BDQ_THREADS), 0, st, h->q, (const unsigned char *)h->Q.unfin, E, M, (flags & BP_QUEUE_FULL_ONLY) ? 1 : 0, ids, counts);
+    HIPCHK(h, hipGetLastError());
+    const int row16 = (int)(row / 16);
+    hipLaunchKernelGGL(k_bdq_gather, dim3((row16 + BDQ_GATHER_THREADS - 1) / BDQ_GATHER_THREADS, M), dim3(BDQ_GATHER_THREADS), 0, st, (const int *)ids,
+                       (const unsigned char *)h->q.fresh, E, (const uint4 *)obs_e, (uint4 *)obs, row16, (const double *)reward_e,
+                       (const unsigned char *)terminated_e, (const unsigned char *)truncated_e, (const double *)info_e, (const int *)slices_e, reward,
+                       terminated, truncated, info, slices, BP_INFO_COUNT);
+    HIPCHK(h, hipGetLastError());
+    return BP_OK;
+}
+
+int bp_bd_queue_send(bp_handle *h, const double *actions, const int32_t *ids, const uint8_t *reset, uint8_t *obs_e, double *info_e, void *stream)
+{
+    if (!h || !actions || !ids) return BP_EINVAL;
+    if (int rc = queue_ready(h, "bp_bd_queue_send")) return rc;
+    if (reset != nullptr && !info_e) return fail(h, BP_EINVAL, "bp_bd_queue_send: reset rows need the envs' info rows");
+    BP_DEVICE(h);
+    hipStream_t st = (hipStream_t)stream;
+    const int E = h->num_envs;
+    hipLaunchKernelGGL(k_bdq_send, dim3(1), dim3(BDQ_THREADS), 0, st, h->q, h->Q.unfin, E, h->q_batch, queue_action_dim(h), actions, (const int *)ids, reset);
+    HIPCHK(h, hipGetLastError());
+    if (reset == nullptr) return BP_OK;
+    // the reset rows: the masked reset of bp_reset with the mask the send kernel built (held envs are not busy: nothing to cancel), then their fresh rows
+    const bool save = h->timing;
+    h->timing = false;
+    const int rc = launch(h, MODE_RESET, nullptr, h->q.rmask, obs_e, nullptr, nullptr, nullptr, info_e, st, true, true);
+    h->timing = save;
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_bdq_enqueue, dim3(1), dim3(BDQ_THREADS), 0, st, h->q, h->Q.unfin, (const unsigned char *)h->q.rmask, E, 1);
+    HIPCHK(h, hipGetLastError());
+    return BP_OK;
+}
+
+int bp_bd_queue_close(bp_handle *h, uint8_t *obs, double *reward, uint8_t *terminated, uint8_t *truncated, double *info, uint8_t *ready, int32_t *slices,
+                      void *stream)
+{
+    if (!h || !reward || !terminated || !truncated || !info || !ready || !slices) return BP_EINVAL;
+    if (int rc = queue_ready(h, "bp_bd_queue_close")) return rc;
+    BP_DEVICE(h);
+    // the drain: the busy envs run to the end of their env steps, held and idle envs emit nothing
+    const AsyncArgs as = {0, ready, slices};
+    if (int rc = launch(h, MODE_DRAIN, nullptr, nullptr, obs, reward, terminated, truncated, info, (hipStream_t)stream, true, true, &as)) return rc;
+    HIPCHK(h, hipMemsetAsync(h->Q.unfin, 0, (size_t)h->num_envs, (hipStream_t)stream));   // every env is idle, the queue is discarded
+    h->async_open = false;
+    h->q_batch = 0;
+    return BP_OK;
+}
+
+int32_t bp_bd_queue_batch(bp_handle *h) { return h ? h->q_batch : 0; }
 
 int bp_observe(bp_handle *h, const uint8_t *env_mask, uint8_t *obs, void *stream)
 {

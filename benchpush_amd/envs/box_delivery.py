@@ -21,7 +21,7 @@ from ..gym_shim import Env, spaces
 from ..scenario import poly_centroid
 from .ship_ice import BatchedShipIceEnv, _ptr
 
-__all__ = ["BatchedBoxDeliveryEnv", "BoxDeliveryEnv", "BD_INFO_KEYS"]
+__all__ = ["BatchedBoxDeliveryEnv", "BoxDeliveryEnv", "AsyncQueue", "BD_INFO_KEYS"]
 BD_INFO_KEYS = _lib.BD_INFO_KEYS
 
 
@@ -139,6 +139,13 @@ class BatchedBoxDeliveryEnv(BatchedShipIceEnv):
                                                             _ptr(self.info), _ptr(ready), _ptr(slices), self._stream()), "bp_bd_async_drain")
         return self.obs, self.reward, self.terminated, self.truncated, self.info, ready
 
+    def async_queue(self, batch_size, budget=None):
+        """Opens a device-resident ready queue on the asynchronous step and returns it (``AsyncQueue``): ``recv()`` hands out exactly `batch_size` rows -- env
+        ids and their transitions, densely packed -- and ``send(actions, ids)`` gives those envs their next actions; no call reads anything back.  The env
+        must have been reset and have no open slice.  budget: sim steps per env and recv (None: the task's ASYNC_BUDGET).  Until the queue's close() or a
+        reset() of all envs, step, step_async, drain, reset(mask), save_state, restore_state and clone_envs raise BpError."""
+        return AsyncQueue(self, batch_size, self.ASYNC_BUDGET if budget is None else budget)
+
     def stragglers(self):
         """(env steps finished by the second pass of the two-pass step, env steps whose path / until-still loop ran into STEP_LIMIT), cumulative since load."""
         out = np.zeros(2, np.uint32)
@@ -186,6 +193,101 @@ class BatchedBoxDeliveryEnv(BatchedShipIceEnv):
         p = lambda a: a.ctypes.data_as(C.c_void_p)
         _lib.check(self.L, self.h, self.L.bp_bd_get_state(self.h, p(alive), p(wp), p(nwp)), "bp_bd_get_state")
         return alive, wp, nwp
+
+
+class AsyncQueue:
+    """Fixed-size recv / send batches over the asynchronous step of a BatchedBoxDeliveryEnv / BatchedAreaClearingEnv (``env.async_queue(M)``; DESIGN.md
+    "Asynchronous step").  The queue between the two lives on the device: a FIFO ring of env ids, filled by the envs that emit a transition (and by reset
+    envs, as *fresh* rows), in the order (call, env id).  All outputs are device tensors allocated once at open and reused by every recv:
+
+    ids int32 [M] (-1 beyond the count), obs uint8 [M, 224, 224, 4], reward float64 [M], terminated / truncated uint8 [M], info float64 [M, 16],
+    slices int32 [M] (calls the transition took; 0 = fresh row: a reset observation with reward 0 and flags 0), emitted uint8 [E] (the slice call's ready
+    mask), counts int32 [5] = rows delivered, ids still queued, busy envs, envs taken and not sent yet, rejected send rows so far."""
+
+    def __init__(self, env, batch_size, budget):
+        self.env, self.batch_size, self.budget = env, int(batch_size), int(budget)
+        if self.budget < 1:
+            raise _lib.BpError("async_queue failed: BP_EINVAL (-1) budget %d < 1 sim step" % self.budget)
+        _lib.check(env.L, env.h, env.L.bp_bd_queue_open(env.h, self.batch_size, env._stream()), "bp_bd_queue_open")
+        M, dv = self.batch_size, env.device
+        env._async_io()
+        self.ids = torch.full((M,), -1, dtype=torch.int32, device=dv)
+        self.obs = torch.zeros((M,) + tuple(env.obs_shape), dtype=torch.uint8, device=dv)
+        self.reward = torch.zeros(M, dtype=torch.float64, device=dv)
+        self.terminated = torch.zeros(M, dtype=torch.uint8, device=dv)
+        self.truncated = torch.zeros(M, dtype=torch.uint8, device=dv)
+        self.info = torch.zeros((M, _lib.INFO_COUNT), dtype=torch.float64, device=dv)
+        self.slices = torch.zeros(M, dtype=torch.int32, device=dv)
+        self.emitted = torch.zeros(env.num_envs, dtype=torch.uint8, device=dv)
+        self.counts = torch.zeros(5, dtype=torch.int32, device=dv)
+        self._counts_sum = torch.zeros(5, dtype=torch.int64, device=dv)   # running sums for stats()
+        self._actions = torch.zeros(M * env.action_dim, dtype=torch.float64, device=dv)
+        self._calls = 0
+
+    @property
+    def is_open(self):
+        """True until close() or a reset() of all envs (a host flag, no device read)."""
+        return bool(self.env.h) and int(self.env.L.bp_bd_queue_batch(self.env.h)) > 0
+
+    def _recv_once(self, flags):
+        v = self.env
+        _lib.check(v.L, v.h, v.L.bp_bd_queue_recv(v.h, self.budget, flags, _ptr(v.obs), _ptr(v.reward), _ptr(v.terminated), _ptr(v.truncated), _ptr(v.info),
+                                                  _ptr(self.emitted), _ptr(v._slices), _ptr(self.ids), _ptr(self.obs), _ptr(self.reward),
+                                                  _ptr(self.terminated), _ptr(self.truncated), _ptr(self.info), _ptr(self.slices), _ptr(self.counts),
+                                                  v._stream()), "bp_bd_queue_recv")
+        self._calls += 1
+        self._counts_sum += self.counts
+
+    def recv(self, block=False):
+        """One slice call of `budget` sim steps per env, then up to M queued rows: returns (ids, obs, reward, terminated, truncated, info), the queue's own
+        [M, ...] tensors (overwritten by the next recv); ``slices``, ``emitted`` and ``counts`` are attributes.  block=False is one library call and
+        synchronises nothing: the batch may be partly filled (ids -1, zero rows).  block=True repeats the call until it delivers a full batch or no env is
+        busy any more, taking nothing in between; it reads the 5-int ``counts`` once per iteration, and that is its only host read."""
+        if not block:
+            self._recv_once(0)
+        else:
+            while True:
+                self._recv_once(_lib.QUEUE_FULL_ONLY)
+                c = self.counts.tolist()
+                if c[0] > 0 or c[2] == 0:
+                    break
+        return self.ids, self.obs, self.reward, self.terminated, self.truncated, self.info
+
+    def send(self, actions, ids, reset=None):
+        """actions [M] (or [M, 2] for velocity actions), ids int32 [M] as a recv returned them, reset uint8 / bool [M] or None: row j hands env ids[j] its
+        next action, or -- reset[j] != 0 -- resets it (next trial, as reset(mask)) and queues its reset observation as a fresh row.  Rows with id -1 are
+        ignored; a row whose env is not awaiting a send, or that a smaller row of the same send already named, is ignored and counted (``counts[4]``).
+        Raises ValueError, before anything is launched, for tensors of the wrong shape, dtype or device.  Synchronises nothing."""
+        v, M = self.env, self.batch_size
+        for name, t in (("actions", actions), ("ids", ids)) + ((("reset", reset),) if reset is not None else ()):
+            if not isinstance(t, torch.Tensor) or t.device.type != v.device.type or (v.device.index is not None and t.device.index != v.device.index):
+                raise ValueError("send: %s must be a tensor on %s" % (name, v.device))
+        if not actions.is_floating_point() or actions.numel() != M * v.action_dim:
+            raise ValueError("send: actions must be a floating-point tensor of %d elements" % (M * v.action_dim))
+        if ids.dtype != torch.int32 or tuple(ids.shape) != (M,):
+            raise ValueError("send: ids must be an int32 tensor of shape [%d]" % M)
+        if reset is not None:
+            if reset.dtype not in (torch.uint8, torch.bool) or tuple(reset.shape) != (M,):
+                raise ValueError("send: reset must be a uint8 or bool tensor of shape [%d]" % M)
+            reset = reset.contiguous().view(torch.uint8)
+        self._actions.copy_(actions.reshape(-1), non_blocking=True)
+        _lib.check(v.L, v.h, v.L.bp_bd_queue_send(v.h, _ptr(self._actions), _ptr(ids.contiguous()), _ptr(reset), _ptr(v.obs), _ptr(v.info), v._stream()),
+                   "bp_bd_queue_send")
+
+    def close(self):
+        """Runs the busy envs to the end of their env steps (the drain), discards the queue and closes the slice; returns drain()'s six-tuple on the env's
+        [E] rows.  Afterwards every env is idle and step(), save_state and the rest work again."""
+        v = self.env
+        ready, slices = v._async_io()
+        _lib.check(v.L, v.h, v.L.bp_bd_queue_close(v.h, _ptr(v.obs), _ptr(v.reward), _ptr(v.terminated), _ptr(v.truncated), _ptr(v.info), _ptr(ready),
+                                                   _ptr(slices), v._stream()), "bp_bd_queue_close")
+        return v.obs, v.reward, v.terminated, v.truncated, v.info, ready
+
+    def stats(self):
+        """Host summary (one device read): recv calls, rows delivered, mean fill of the batch, rejected send rows."""
+        s = self._counts_sum.tolist()
+        rejected = int(self.counts[4].item()) if self._calls else 0
+        return {"calls": self._calls, "rows": int(s[0]), "mean_fill": (s[0] / (self._calls * self.batch_size)) if self._calls else 0.0, "rejected": rejected}
 
 
 def low_dim_observation(polys):

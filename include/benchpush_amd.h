@@ -392,6 +392,41 @@ int bp_bd_step_async(bp_handle *h, const double *actions, int32_t budget, uint8_
 int bp_bd_async_drain(bp_handle *h, uint8_t *obs, double *reward, uint8_t *terminated, uint8_t *truncated, double *info, uint8_t *ready,
                       int32_t *slices, void *stream);
 int32_t bp_bd_async_open(bp_handle *h);
+/* Ready queue of the asynchronous step: fixed-size recv / send batches, the queue between the two on the device (opt-in; the calls above are unchanged).
+ * With a queue open every env is idle (has an action, starts in the next recv), busy, or held: it emitted a transition or was reset and waits in the queue
+ * or for its send.  The queue is a FIFO ring of env ids with capacity E; an env is in it at most once.  Its order is a function of the handle's history
+ * alone: enqueue events (open, recvs, sends) in stream order, ascending env id within one event.
+ *   bp_bd_queue_open(batch = M, 1 <= M <= E): needs a handle that was reset and has no open slice.  Every env becomes held and is queued, in env-id order,
+ *     as a fresh row: its current observation and info row, no transition.  Opens the slice (bp_bd_async_open is 1).
+ *   bp_bd_queue_recv(budget >= 1, flags): one slice call exactly as bp_bd_step_async launches it, writing the [E] rows obs_e / reward_e / terminated_e /
+ *     truncated_e / info_e / slices_e of the envs that emitted and emitted[E] (that call's ready mask); then the envs that emitted are appended in ascending
+ *     env id and become held, up to M ids leave the head into ids[M] (int32), and row j of obs [M][rows of obs_e] / reward [M] / terminated [M] /
+ *     truncated [M] / info [M][BP_INFO_COUNT] / slices [M] gets the rows of env ids[j].  A fresh row has reward 0, flags 0 and slices 0; rows beyond the
+ *     count have ids[j] = -1 and zeros.  counts (int32 [5]): rows delivered, ids still queued, busy envs, envs taken and not sent yet (these rows included),
+ *     rejected send rows so far.  With BP_QUEUE_FULL_ONLY in flags nothing is taken (count 0) while fewer than M ids are queued and an env is still
+ *     busy: a caller that wants full batches repeats the call.  obs_e and obs may both be NULL (no observations); otherwise a row is a multiple of 16 bytes and both are 16-byte aligned.
+ *   bp_bd_queue_send(actions [M][action dim], ids [M], reset [M] or NULL): row j with ids[j] >= 0 hands env ids[j] its next action -- the env is idle and starts
+ *     in the next recv -- or, with reset[j] != 0, resets it as bp_reset with a mask does (next trial, the episode closes in the episode metrics; obs_e /
+ *     info_e get the rows) and queues it as a fresh row, reset rows of one send in ascending env id; the env stays held.  Rows with ids[j] == -1 are ignored.
+ *     A row is rejected -- ignored, and counted in counts[4] -- if its env is not taken and awaiting its send (out of range, busy, idle, still queued) or if a
+ *     smaller row of the same send names the same env.  reset == NULL launches no reset kernel.
+ *   bp_bd_queue_close: the drain (the busy envs finish, outputs as bp_bd_async_drain), then the queue is discarded, every env is idle and the slice is closed.
+ *     A bp_reset of all envs closes the queue too, without the drain.
+ *   bp_bd_queue_batch: M while a queue is open, else 0 (a host flag).
+ * While a queue is open bp_bd_step_async, bp_bd_async_drain and bp_reset with a mask return BP_ESTATE like the calls an open slice refuses; nothing is launched.
+ * State records carry neither queue nor loop state.  Nothing synchronises and nothing is read back; all work is enqueued on `stream`; all tensors are device
+ * memory.  BP_EINVAL: NULL handle or tensor, batch outside [1, E], budget < 1, a handle of another environment or one with damping != 0; BP_ESTATE: before
+ * load and reset, open on an open slice, recv / send / close without a queue.  A recv that fails part-way leaves the handle open and refusing, as
+ * bp_bd_step_async.  (Added within ABI 11: the additions only add.) */
+int bp_bd_queue_open(bp_handle *h, int32_t batch, void *stream);
+#define BP_QUEUE_FULL_ONLY 1   /* bp_bd_queue_recv flags: take nothing while fewer than M ids are queued and an env is still busy */
+int bp_bd_queue_recv(bp_handle *h, int32_t budget, int32_t flags, uint8_t *obs_e, double *reward_e, uint8_t *terminated_e, uint8_t *truncated_e, double *info_e,
+                     uint8_t *emitted, int32_t *slices_e, int32_t *ids, uint8_t *obs, double *reward, uint8_t *terminated, uint8_t *truncated,
+                     double *info, int32_t *slices, int32_t *counts, void *stream);
+int bp_bd_queue_send(bp_handle *h, const double *actions, const int32_t *ids, const uint8_t *reset, uint8_t *obs_e, double *info_e, void *stream);
+int bp_bd_queue_close(bp_handle *h, uint8_t *obs, double *reward, uint8_t *terminated, uint8_t *truncated, double *info, uint8_t *ready, int32_t *slices,
+                      void *stream);
+int32_t bp_bd_queue_batch(bp_handle *h);
 /* tests: per-env box bookkeeping, host buffers: alive uint8 [E][24], waypoints double [E][64][3], nwp int32 [E] (synchronises) */
 int bp_bd_get_state(bp_handle *h, uint8_t *alive, double *waypoints, int32_t *nwp);
 
