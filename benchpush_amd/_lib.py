@@ -35,7 +35,8 @@ EXPORTS = ["bp_abi_version", "bp_create", "bp_destroy", "bp_load_scenarios", "bp
            "bp_sizeof_rrt_config", "bp_rrt_workspace_bytes", "bp_rrt_uniform", "bp_rrt_plan", "bp_sizeof_track_wp_config", "bp_track_waypoints",
            "bp_sizeof_gtsp_config", "bp_gtsp_workspace_bytes", "bp_gtsp_plan", "bp_gtsp_track",
            "bp_bd_step_async", "bp_bd_async_drain", "bp_bd_async_open", "bp_bd_get_episode_boxes", "bp_bd_get_completed", "bp_task_metric_row",
-           "bp_bd_queue_open", "bp_bd_queue_recv", "bp_bd_queue_send", "bp_bd_queue_close", "bp_bd_queue_batch"]
+           "bp_bd_queue_open", "bp_bd_queue_recv", "bp_bd_queue_send", "bp_bd_queue_close", "bp_bd_queue_batch",
+           "bp_sizeof_replay_desc", "bp_sizeof_replay_batch", "bp_replay_index", "bp_replay_observe", "bp_replay_record", "bp_replay_sample"]
 GTSP_OK, GTSP_NOTHING_TO_PUSH, GTSP_SKIPPED, GTSP_CAP, GTSP_INVALID = range(5)
 GTSP_STATUS_MASK, GTSP_FLAG_VANISHED, GTSP_FLAG_DEGENERATE = 0xFF, 0x100, 0x200   # status = code | flags
 GTSP_MAX_BOXES, GTSP_MAX_GOALS, GTSP_MAX_SLOTS = 12, 8, 64
@@ -58,6 +59,17 @@ class BpCostmapConfig(C.Structure):
 class BpSwathConfig(C.Structure):
     _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("K", C.c_int32), ("P", C.c_int32), ("nv", C.c_int32), ("outside", C.c_int32),
                 ("map_stride", C.c_int64)]
+
+
+class BpReplayDesc(C.Structure):
+    _fields_ = [("capacity", C.c_int32), ("num_envs", C.c_int32), ("device", C.c_int32), ("action_dim", C.c_int32), ("row_bytes", C.c_int64),
+                ("max_rows", C.c_int32), ("pad_", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("state", "next_state", "action", "reward", "ministeps", "nonfinal", "env", "pend_obs", "pend_action",
+                                          "pend_flags", "hdr", "row_slot", "win")]
+
+
+class BpReplayBatch(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("state", "next_state", "action", "reward", "ministeps", "nonfinal", "slot", "valid")]
 
 
 class BpLatticeConfig(C.Structure):
@@ -287,6 +299,16 @@ def load():
         L.bp_gtsp_workspace_bytes.restype = C.c_int64
         L.bp_gtsp_plan.argtypes = [vp, C.POINTER(BpGtspConfig), vp, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_int64] + [vp] * 10
         L.bp_gtsp_track.argtypes = [vp, C.POINTER(BpGtspConfig)] + [vp] * 9
+    if hasattr(L, "bp_replay_observe"):   # replay buffer on the ready queue (absent from older builds loaded for same-box comparisons)
+        L.bp_sizeof_replay_desc.restype = C.c_int32
+        L.bp_sizeof_replay_batch.restype = C.c_int32
+        if L.bp_sizeof_replay_desc() != C.sizeof(BpReplayDesc) or L.bp_sizeof_replay_batch() != C.sizeof(BpReplayBatch):
+            raise BpError("bp_replay_desc / bp_replay_batch layout mismatch between _lib and the library")
+        L.bp_replay_index.argtypes = [C.c_uint64, C.c_int64, C.c_int32, C.c_int64]
+        L.bp_replay_index.restype = C.c_int64
+        L.bp_replay_observe.argtypes = [C.POINTER(BpReplayDesc)] + [vp] * 7 + [C.c_int32, C.c_int32, vp]
+        L.bp_replay_record.argtypes = [C.POINTER(BpReplayDesc), vp, vp, vp, C.c_int32, vp]
+        L.bp_replay_sample.argtypes = [C.POINTER(BpReplayDesc), C.c_int32, C.c_uint64, C.POINTER(BpReplayBatch), vp]
     _lib = L
     return L
 

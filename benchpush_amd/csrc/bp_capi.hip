@@ -27,6 +27,7 @@
 #include "bp_rrt.hpp"
 #include "bp_gtsp.hpp"
 #include "bp_asyncq.hpp"
+#include "bp_replay.hpp"
 
 struct bp_handle {
     bp_config cfg;
@@ -2592,6 +2593,70 @@ int bp_set_resettle(bp_handle *h, int32_t on)
     if (!h) return BP_EINVAL;
     h->resettle = (on != 0) || (h->P.random_start != 0); // per-episode start poses always settle in place
     return BP_OK;
+}
+
+// ---- replay buffer on the ready queue (bp_replay.hpp): handle-free, the caller owns the memory ----
+int32_t bp_sizeof_replay_desc(void) { return (int32_t)sizeof(bp_replay_desc); }
+int32_t bp_sizeof_replay_batch(void) { return (int32_t)sizeof(bp_replay_batch); }
+int64_t bp_replay_index(uint64_t seed, int64_t draw, int32_t b, int64_t n)
+{
+    if (n < 1 || n > 0x7FFFFFFFll || b < 0) return -1;
+    return bp_replay_pick(seed, draw, b, n);
+}
+static int replay_buf(const bp_replay_desc *d, ReplayBuf *r)
+{
+    if (!d || !d->state || !d->next_state || !d->action || !d->reward || !d->ministeps || !d->nonfinal || !d->env || !d->pend_obs || !d->pend_action ||
+        !d->pend_flags || !d->hdr || !d->row_slot || !d->win)
+        return BP_EINVAL;
+    if (d->capacity < 1 || d->num_envs < 1 || d->action_dim != 1 || d->max_rows < 1 || d->device < 0) return BP_EINVAL;
+    if (d->row_bytes < 16 || d->row_bytes % 16 != 0 || d->row_bytes / 16 > 0x7FFFFFFFll) return BP_EINVAL;
+    if ((((uintptr_t)d->state | (uintptr_t)d->next_state | (uintptr_t)d->pend_obs) & 15u) != 0) return BP_EINVAL;
+    r->C = d->capacity; r->E = d->num_envs; r->row16 = (int)(d->row_bytes / 16);
+    r->state = (uint4 *)d->state; r->next_state = (uint4 *)d->next_state; r->action = d->action; r->reward = d->reward; r->ministeps = d->ministeps;
+    r->nonfinal = d->nonfinal; r->env = d->env; r->pend_obs = (uint4 *)d->pend_obs; r->pend_action = d->pend_action; r->pend_flags = d->pend_flags;
+    r->hdr = (long long *)d->hdr; r->row_slot = d->row_slot; r->win = d->win;
+    return BP_OK;
+}
+static int replay_pieces(const ReplayBuf &r) { return (r.row16 + RPL_COPY_THREADS - 1) / RPL_COPY_THREADS; }
+int bp_replay_observe(const bp_replay_desc *d, const int32_t *ids, const uint8_t *obs, const double *reward, const uint8_t *terminated,
+                      const uint8_t *truncated, const double *info, const int32_t *slices, int32_t M, int32_t ministeps_col, void *stream)
+{
+    ReplayBuf r;
+    if (replay_buf(d, &r) != BP_OK || !ids || !obs || !reward || !terminated || !truncated || !info || !slices) return BP_EINVAL;
+    if (M < 1 || M > d->max_rows || ministeps_col < 0 || ministeps_col >= BP_INFO_COUNT || (((uintptr_t)obs) & 15u) != 0) return BP_EINVAL;
+    if (replay_pieces(r) > 65535) return BP_EINVAL;
+    DevGuard dg(d->device);
+    if (!dg.ok) return BP_EHIP;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_replay_plan, dim3(1), dim3(RPL_THREADS), 0, st, r, (const int *)ids, reward, (const unsigned char *)terminated, info,
+                       (const int *)slices, M, BP_INFO_COUNT, ministeps_col);
+    hipLaunchKernelGGL(k_replay_copy, dim3(M, replay_pieces(r)), dim3(RPL_COPY_THREADS), 0, st, r, (const int *)ids, (const uint4 *)obs);
+    return hipGetLastError() == hipSuccess ? BP_OK : BP_EHIP;
+}
+int bp_replay_record(const bp_replay_desc *d, const double *actions, const int32_t *ids, const uint8_t *reset, int32_t M, void *stream)
+{
+    ReplayBuf r;
+    if (replay_buf(d, &r) != BP_OK || !actions || !ids || M < 1) return BP_EINVAL;
+    DevGuard dg(d->device);
+    if (!dg.ok) return BP_EHIP;
+    hipLaunchKernelGGL(k_replay_record, dim3(1), dim3(RPL_THREADS), 0, (hipStream_t)stream, r, actions, (const int *)ids, (const unsigned char *)reset, M);
+    return hipGetLastError() == hipSuccess ? BP_OK : BP_EHIP;
+}
+int bp_replay_sample(const bp_replay_desc *d, int32_t B, uint64_t seed, const bp_replay_batch *out, void *stream)
+{
+    ReplayBuf r;
+    if (replay_buf(d, &r) != BP_OK || !out || B < 1) return BP_EINVAL;
+    if (!out->state || !out->next_state || !out->action || !out->reward || !out->ministeps || !out->nonfinal || !out->slot || !out->valid) return BP_EINVAL;
+    if ((((uintptr_t)out->state | (uintptr_t)out->next_state) & 15u) != 0 || replay_pieces(r) > 65535) return BP_EINVAL;
+    ReplayBatch o;
+    o.state = out->state; o.next_state = out->next_state; o.action = (long long *)out->action; o.reward = out->reward; o.ministeps = out->ministeps;
+    o.nonfinal = out->nonfinal; o.slot = out->slot; o.valid = out->valid;
+    DevGuard dg(d->device);
+    if (!dg.ok) return BP_EHIP;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_replay_pick, dim3(1), dim3(RPL_THREADS), 0, st, r, o, B, (unsigned long long)seed);
+    hipLaunchKernelGGL(k_replay_gather, dim3(B, replay_pieces(r)), dim3(RPL_COPY_THREADS), 0, st, r, o);
+    return hipGetLastError() == hipSuccess ? BP_OK : BP_EHIP;
 }
 
 // debug hook of the diagnostic twin (-DBP_DEBUG_PATHS): trace (x, y, angle) of every body of one env after each sub-step of the next

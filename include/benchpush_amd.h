@@ -731,6 +731,68 @@ int bp_gtsp_plan(bp_handle *h, const bp_gtsp_config *cfg, const double *poses, c
 int bp_gtsp_track(bp_handle *h, const bp_gtsp_config *cfg, const double *paths, const int32_t *lengths, const double *poses, const uint8_t *active,
                   int32_t *track_id, double *track_setpoint, double *actions, int32_t *diag, void *stream);
 
+/* ---- replay buffer on the ready queue (DESIGN.md "Replay buffer") ----
+ * Handle-free: the caller owns every array (device memory on `device`) and passes them in a bp_replay_desc.  C = capacity, E = num_envs, R = row_bytes
+ * (P * P * 4, a multiple of 16; every observation array 16-byte aligned).
+ *   ring     state, next_state uint8 [C][R]; action int32 [C]; reward, ministeps float [C]; nonfinal uint8 [C]; env int32 [C]
+ *   per env  pend_obs uint8 [E][R]; pend_action int32 [E]; pend_flags uint8 [E]: bit 0 an observation is held, bit 1 an action is recorded,
+ *            bit 2 the env awaits a record
+ *   hdr      int64 [4]: transitions ever stored, sample draws made, transition rows dropped for want of a pending observation or action, rejected record rows
+ *   workspace row_slot int32 [max_rows], win int32 [E] (contents are scratch)
+ * All of it starts as zeros.
+ *
+ * bp_replay_observe takes the outputs of one bp_bd_queue_recv (M <= max_rows rows; info is [M][BP_INFO_COUNT], ministeps_col its column of info['ministeps']).
+ * Rows with ids[j] = e in [0, E) are handled in ascending j (other rows are ignored).  A row is a transition row if slices[j] > 0 and bits 0 and 1 of e are
+ * set; it is stored at slot (hdr[0] + rank) % C, rank its rank among the call's transition rows: state = pend_obs[e], next_state = obs[j], action =
+ * pend_action[e], reward = (float)reward[j], ministeps = (float)info[j][ministeps_col], nonfinal = !terminated[j] (the reference builds no next observation
+ * for a terminated step; truncated is accepted and not read), env = e.  A row with slices[j] > 0 that lacks a bit stores nothing and counts in hdr[2].
+ * Then every handled row, fresh rows (slices 0) included, makes obs[j] the pending observation of e and sets its flags to bit 0 | bit 2.  hdr[0] grows by
+ * the number of transition rows; if more than C arrive in one call the later ones overwrite the earlier ones in row order.  The ids of one call must be
+ * distinct, as the queue's are.
+ *
+ * bp_replay_record takes what is passed to bp_bd_queue_send (action_dim 1; reset [M] or NULL).  Row j is accepted if ids[j] = e in [0, E), bit 2 of e is set
+ * and j is the smallest row naming e.  Accepted without reset: pend_action[e] = (int)actions[j], bit 1 set, bit 2 cleared; accepted with reset[j] != 0: all
+ * bits cleared.  Every other row with ids[j] >= 0 counts in hdr[3].
+ *
+ * bp_replay_sample draws B transitions with replacement: n = min(hdr[0], C) on the device, sample b takes slot bp_replay_index(seed, hdr[1], b, n), then
+ * hdr[1] grows by one.  out: state, next_state float [B][4][P][P] (channel first, (float)u8 / 255.0f by IEEE division), action int64 [B], reward, ministeps
+ * float [B], nonfinal uint8 [B], slot int32 [B], valid uint8 [B] = 1 when n > 0; with n == 0 every output is zero.  The float planes are 16-byte aligned.
+ * bp_replay_index is a host function, the kernel's index rule: the high 32 bits r of the project's counter RNG keyed by (seed, draw, b), (r * n) >> 32;
+ * -1 for n outside 1 .. 2^31 - 1.
+ *
+ * Nothing synchronises, nothing is read back; all work is enqueued on `stream`.  BP_EINVAL, before anything is launched: a NULL pointer, row_bytes % 16 != 0,
+ * capacity < 1, num_envs < 1, action_dim != 1, M or B < 1, M > max_rows, ministeps_col outside the info row.  (Added within ABI 11: the additions only add.) */
+typedef struct bp_replay_desc {
+    int32_t capacity, num_envs, device, action_dim;
+    int64_t row_bytes;
+    int32_t max_rows, pad_;
+    uint8_t *state, *next_state;
+    int32_t *action;
+    float *reward, *ministeps;
+    uint8_t *nonfinal;
+    int32_t *env;
+    uint8_t *pend_obs;
+    int32_t *pend_action;
+    uint8_t *pend_flags;
+    int64_t *hdr;
+    int32_t *row_slot, *win;
+} bp_replay_desc;
+typedef struct bp_replay_batch {
+    float *state, *next_state;
+    int64_t *action;
+    float *reward, *ministeps;
+    uint8_t *nonfinal;
+    int32_t *slot;
+    uint8_t *valid;
+} bp_replay_batch;
+int32_t bp_sizeof_replay_desc(void);
+int32_t bp_sizeof_replay_batch(void);
+int64_t bp_replay_index(uint64_t seed, int64_t draw, int32_t b, int64_t n);
+int bp_replay_observe(const bp_replay_desc *d, const int32_t *ids, const uint8_t *obs, const double *reward, const uint8_t *terminated,
+                      const uint8_t *truncated, const double *info, const int32_t *slices, int32_t M, int32_t ministeps_col, void *stream);
+int bp_replay_record(const bp_replay_desc *d, const double *actions, const int32_t *ids, const uint8_t *reset, int32_t M, void *stream);
+int bp_replay_sample(const bp_replay_desc *d, int32_t B, uint64_t seed, const bp_replay_batch *out, void *stream);
+
 const char *bp_last_error(const bp_handle *h);
 int32_t bp_abi_version(void);
 int32_t bp_sizeof_config(void);   /* sizeof(bp_config), so a binding can verify its struct layout */
