@@ -873,6 +873,7 @@ __global__ __launch_bounds__(256) void k_episode_metrics(const DevParams P, cons
 #include "bp_taskmetric.hpp"   // k_task_metrics: the same for box-delivery / area-clearing handles (needs bp_round2)
 
 enum { MODE_ASYNC = 2, MODE_DRAIN = 3 };   // box-delivery / area-clearing: bp_bd_step_async, bp_bd_async_drain
+struct StepOut { unsigned char *obs; double *reward; unsigned char *term, *trunc; double *info; };   // the output rows of a launch, null where a call has none
 struct AsyncArgs {                         // what those two calls hand to launch() beside the step's outputs
     int budget;                            // sim steps per env and call (0: no limit, the drain)
     unsigned char *ready;                  // [E]
@@ -892,160 +893,159 @@ static int bd_side_streams(bp_handle *h, bool two_pass)
     if (!h->ev_join3) HIPCHK(h, hipEventCreateWithFlags(&h->ev_join3, hipEventDisableTiming));
     return BP_OK;
 }
-static int launch(bp_handle *h, int mode, const double *actions, const unsigned char *mask, unsigned char *obs, double *reward,
-                  unsigned char *term, unsigned char *trunc, double *info, hipStream_t st, bool physics, bool raster, const AsyncArgs *as = nullptr)
+// The task's finish kernel for the envs that Bx selects; init: the episode-start bookkeeping of the trials' template slots instead (bp_bd_load).
+static int bd_finish(bp_handle *h, const BdParams &Bx, hipStream_t s, const StepOut &out, int init = 0)
 {
-    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
-    if (h->timing) {
-        if (h->ev_used + 3 > h->ev.size()) {
-            for (int k = 0; k < 3; k++) { hipEvent_t e; HIPCHK(h, hipEventCreate(&e)); h->ev.push_back(e); }
-        }
-        e0 = h->ev[h->ev_used]; e1 = h->ev[h->ev_used + 1]; e2 = h->ev[h->ev_used + 2];
-        h->ev_used += 3;
-        HIPCHK(h, hipEventRecord(e0, st));
+    const dim3 grid(init ? h->num_trials : h->num_envs);
+    if (h->B.task == 1) hipLaunchKernelGGL(k_ac_finish, grid, dim3(64), h->bd_lds, s, h->P, h->D, Bx, h->Q, init, init, out.reward, out.term, out.trunc, out.info);
+    else hipLaunchKernelGGL(k_bd_finish, grid, dim3(64), h->bd_lds, s, h->P, h->D, Bx, h->Q, init, init, out.reward, out.term, out.trunc, out.info);
+    HIPCHK(h, hipGetLastError());
+    return BP_OK;
+}
+static int bd_observe(bp_handle *h, const BdParams &Bx, hipStream_t s, const unsigned char *mask, unsigned char *obs)
+{
+    hipLaunchKernelGGL(k_bd_observe, dim3(h->num_envs), dim3(BDO_THREADS), h->bd_obs_lds, s, h->P, h->D, Bx, h->Q, mask, obs);
+    HIPCHK(h, hipGetLastError());
+    return BP_OK;
+}
+// The tail of an env step for the envs that Bx selects (Q.unfin[e] == Bx.sel_want; -1: all): the robot's spfa map, which needs only the robot pose, on `side`
+// beside the finish kernel on `st`, the join, and with `obs` their observation.  The caller has recorded ev_fork behind the physics kernel.  side == st: the
+// stream orders the two by itself, the map first, and one error check serves both launches.
+static int bd_tail(bp_handle *h, const BdParams &Bx, hipStream_t st, hipStream_t side, const StepOut &out, unsigned char *obs)
+{
+    if (side != st) HIPCHK(h, hipStreamWaitEvent(side, h->ev_fork, 0));
+    hipLaunchKernelGGL(k_bd_robot_map, dim3(h->num_envs), dim3(BDR_THREADS), h->bd_rmap_lds, side, h->P, h->D, Bx, h->Q, 0);
+    if (side != st) {
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipEventRecord(h->ev_join, side));
     }
-    if (h->P.env_kind == BP_ENV_BOX) {
-        const int E = h->num_envs;
-        if (physics) {
-            if (mode == MODE_STEP) {
-                if (h->steps_done) {
-                    hipLaunchKernelGGL(k_make_order, dim3(1), dim3(1024), 0, st, (const unsigned *)h->D.e_cost, h->order_buf, E, (unsigned *)nullptr);
-                    HIPCHK(h, hipGetLastError());
-                    h->D.order = h->order_buf;
-                }
-                h->steps_done = true;
-                hipLaunchKernelGGL(k_bd_plan, dim3(E), dim3(64), h->bd_lds, st, h->P, h->D, h->B, h->Q, actions);
-                HIPCHK(h, hipGetLastError());
-                if (int rc = bd_side_streams(h, true)) return rc;
-                auto finish = [&](const BdParams &Bx, hipStream_t s_) {
-                    if (h->B.task == 1) hipLaunchKernelGGL(k_ac_finish, dim3(E), dim3(64), h->bd_lds, s_, h->P, h->D, Bx, h->Q, 0, 0, reward, term, trunc, info);
-                    else hipLaunchKernelGGL(k_bd_finish, dim3(E), dim3(64), h->bd_lds, s_, h->P, h->D, Bx, h->Q, 0, 0, reward, term, trunc, info);
-                };
-                if (h->bd_budget > 0) {
-                    // Two-pass step: a launch of k_bd_physics lasts as long as its slowest env, and the slowest are single wavefronts inside the reference's own
-                    // 10 001-step loops.  Pass 0 gives every env `bd_budget` sim steps; the envs that are done -- all but a handful -- go through
-                    // finish / robot map / observation on the caller's stream while pass 1 carries the others to their end on a third stream, followed by the
-                    // same kernels for that group.  Results are those of the single pass (the loop state travels through Q.rs_*, bodies and arbiters through the
-                    // ordinary store / load of a step boundary).
-                    BdParams B0 = h->B, B1 = h->B, Bs0 = h->B, Bs1 = h->B;
-                    B0.budget = h->bd_budget; B0.pass = 0; B1.pass = 1; Bs0.sel_want = 0; Bs1.sel_want = 1;
-                    if (h->damp) hipLaunchKernelGGL(k_bd_physics_damp, dim3(E), dim3(64), h->lds_bytes, st, h->P, h->D, B0, h->Q);
-                    else hipLaunchKernelGGL(k_bd_physics, dim3(E), dim3(64), h->lds_bytes, st, h->P, h->D, B0, h->Q);
-                    HIPCHK(h, hipGetLastError());
-                    HIPCHK(h, hipEventRecord(h->ev_fork, st));
-                    // group 1 (unfinished): third stream
-                    HIPCHK(h, hipStreamWaitEvent(h->st_aux2, h->ev_fork, 0));
-                    if (h->damp) hipLaunchKernelGGL(k_bd_physics_damp, dim3(E), dim3(64), h->lds_bytes, h->st_aux2, h->P, h->D, B1, h->Q);
-                    else if (h->B.cycle_skip > 0) {
-                        // the envs that stopped inside execute_robot_path: the kernel with the recurrence test (a robot pushing against a wall is over after a
-                        // handful of sim steps there); then the others -- the reference's own until-still loops -- on the lean kernel
-                        // (side by side on two streams: an env that pushes boxes through a long path is neither)
-                        BdParams B1p = B1, B1s = B1;
-                        B1p.resume_sel = 1; B1s.resume_sel = 2;
-                        HIPCHK(h, hipStreamWaitEvent(h->st_aux3, h->ev_fork, 0));
-                        hipLaunchKernelGGL(k_bd_physics_resume, dim3(E), dim3(64), h->lds_bytes, h->st_aux3, h->P, h->D, B1p, h->Q);
-                        HIPCHK(h, hipGetLastError());
-                        HIPCHK(h, hipEventRecord(h->ev_join3, h->st_aux3));
-                        hipLaunchKernelGGL(k_bd_physics, dim3(E), dim3(64), h->lds_bytes, h->st_aux2, h->P, h->D, B1s, h->Q);
-                        HIPCHK(h, hipGetLastError());
-                        HIPCHK(h, hipStreamWaitEvent(h->st_aux2, h->ev_join3, 0));
-                    } else hipLaunchKernelGGL(k_bd_physics, dim3(E), dim3(64), h->lds_bytes, h->st_aux2, h->P, h->D, B1, h->Q);
-                    HIPCHK(h, hipGetLastError());
-                    hipLaunchKernelGGL(k_bd_robot_map, dim3(E), dim3(BDR_THREADS), h->bd_rmap_lds, h->st_aux2, h->P, h->D, Bs1, h->Q, 0);
-                    finish(Bs1, h->st_aux2);
-                    HIPCHK(h, hipGetLastError());
-                    if (raster && obs) {
-                        hipLaunchKernelGGL(k_bd_observe, dim3(E), dim3(BDO_THREADS), h->bd_obs_lds, h->st_aux2, h->P, h->D, Bs1, h->Q, (const unsigned char *)nullptr, obs);
-                        HIPCHK(h, hipGetLastError());
-                    }
-                    HIPCHK(h, hipEventRecord(h->ev_join2, h->st_aux2));
-                    // group 0 (done in pass 0): the caller's stream, the robot map beside the finish kernel as before
-                    HIPCHK(h, hipStreamWaitEvent(h->st_aux, h->ev_fork, 0));
-                    hipLaunchKernelGGL(k_bd_robot_map, dim3(E), dim3(BDR_THREADS), h->bd_rmap_lds, h->st_aux, h->P, h->D, Bs0, h->Q, 0);
-                    HIPCHK(h, hipGetLastError());
-                    HIPCHK(h, hipEventRecord(h->ev_join, h->st_aux));
-                    finish(Bs0, st);
-                    HIPCHK(h, hipGetLastError());
-                    HIPCHK(h, hipStreamWaitEvent(st, h->ev_join, 0));
-                    if (raster && obs) {
-                        hipLaunchKernelGGL(k_bd_observe, dim3(E), dim3(BDO_THREADS), h->bd_obs_lds, st, h->P, h->D, Bs0, h->Q, (const unsigned char *)nullptr, obs);
-                        HIPCHK(h, hipGetLastError());
-                        raster = false;   // both groups' observations are on their way
-                    }
-                    HIPCHK(h, hipStreamWaitEvent(st, h->ev_join2, 0));
-                } else {
-                if (h->damp) hipLaunchKernelGGL(k_bd_physics_damp, dim3(E), dim3(64), h->lds_bytes, st, h->P, h->D, h->B, h->Q);
-                else hipLaunchKernelGGL(k_bd_physics, dim3(E), dim3(64), h->lds_bytes, st, h->P, h->D, h->B, h->Q);
-                HIPCHK(h, hipGetLastError());
-                // the robot's spfa map needs only the robot pose: it runs beside the finish kernel on a second stream
-                HIPCHK(h, hipEventRecord(h->ev_fork, st));
-                HIPCHK(h, hipStreamWaitEvent(h->st_aux, h->ev_fork, 0));
-                hipLaunchKernelGGL(k_bd_robot_map, dim3(E), dim3(BDR_THREADS), h->bd_rmap_lds, h->st_aux, h->P, h->D, h->B, h->Q, 0);
-                HIPCHK(h, hipGetLastError());
-                HIPCHK(h, hipEventRecord(h->ev_join, h->st_aux));
-                finish(h->B, st);
-                HIPCHK(h, hipGetLastError());
-                HIPCHK(h, hipStreamWaitEvent(st, h->ev_join, 0));
-                }
-                // episode metrics of the step (TaskDrivenMetric): both groups' finish kernels have joined the caller's stream
-                hipLaunchKernelGGL(k_task_metrics, dim3((E + 255) / 256), dim3(256), 0, st, h->P, h->B, h->D, h->Q, 0, (const unsigned char *)nullptr, (const unsigned char *)nullptr);
-                HIPCHK(h, hipGetLastError());
-            } else if (mode == MODE_ASYNC || mode == MODE_DRAIN) {
-                // Asynchronous step (bp_bd_step_async / bp_bd_async_drain, DESIGN.md "Asynchronous step"): idle envs are planned and started, busy ones resumed, each
-                // runs at most `as->budget` sim steps; the envs whose env step ended (group byte 0) go through the tail kernels exactly as in the one-pass step.
-                // (Dispatch order: h->D.order is what the last lock-step step left, or none -- any permutation serves.)
-                if (int rc = bd_side_streams(h, false)) return rc;
-                const int epoch = ++h->as_epoch;
-                BdParams Bp = h->B, Bl = h->B, Bt = h->B;
-                Bp.pass = Bl.pass = (mode == MODE_ASYNC) ? 2 : 3;
-                Bp.budget = Bl.budget = (mode == MODE_ASYNC) ? as->budget : 0;
-                Bp.resume_sel = 1; Bl.resume_sel = 2; Bt.sel_want = 0;
-                if (mode == MODE_ASYNC) {
-                    hipLaunchKernelGGL(k_bd_plan_async, dim3(E), dim3(64), h->bd_lds, st, h->P, h->D, h->B, h->Q, actions);
-                    HIPCHK(h, hipGetLastError());
-                }
-                // first the busy envs that stopped inside execute_robot_path (the kernel with the recurrence test), then every other env on the lean kernel
-                if (h->B.cycle_skip > 0) {
-                    hipLaunchKernelGGL(k_bd_slice_resume, dim3(E), dim3(64), h->lds_bytes, st, h->P, h->D, Bp, h->Q, as->ready, as->slices, epoch);
-                    HIPCHK(h, hipGetLastError());
-                } else Bl.resume_sel = 0;
-                hipLaunchKernelGGL(k_bd_slice, dim3(E), dim3(64), h->lds_bytes, st, h->P, h->D, Bl, h->Q, as->ready, as->slices, epoch);
-                HIPCHK(h, hipGetLastError());
-                HIPCHK(h, hipEventRecord(h->ev_fork, st));
-                HIPCHK(h, hipStreamWaitEvent(h->st_aux, h->ev_fork, 0));
-                hipLaunchKernelGGL(k_bd_robot_map, dim3(E), dim3(BDR_THREADS), h->bd_rmap_lds, h->st_aux, h->P, h->D, Bt, h->Q, 0);
-                HIPCHK(h, hipGetLastError());
-                HIPCHK(h, hipEventRecord(h->ev_join, h->st_aux));
-                if (h->B.task == 1) hipLaunchKernelGGL(k_ac_finish, dim3(E), dim3(64), h->bd_lds, st, h->P, h->D, Bt, h->Q, 0, 0, reward, term, trunc, info);
-                else hipLaunchKernelGGL(k_bd_finish, dim3(E), dim3(64), h->bd_lds, st, h->P, h->D, Bt, h->Q, 0, 0, reward, term, trunc, info);
-                HIPCHK(h, hipGetLastError());
-                HIPCHK(h, hipStreamWaitEvent(st, h->ev_join, 0));
-                // episode metrics: only the envs that emitted a transition in this call are accounted
-                hipLaunchKernelGGL(k_task_metrics, dim3((E + 255) / 256), dim3(256), 0, st, h->P, h->B, h->D, h->Q, 0, (const unsigned char *)nullptr, (const unsigned char *)as->ready);
-                HIPCHK(h, hipGetLastError());
-                if (raster && obs) {
-                    hipLaunchKernelGGL(k_bd_observe, dim3(E), dim3(BDO_THREADS), h->bd_obs_lds, st, h->P, h->D, Bt, h->Q, (const unsigned char *)nullptr, obs);
-                    HIPCHK(h, hipGetLastError());
-                }
-                raster = false;   // only the envs that emitted a transition get a new observation
-            } else {
-                hipLaunchKernelGGL(k_reset_copy, dim3(E), dim3(256), 0, st, h->P, h->D, mask, (double *)nullptr);
-                HIPCHK(h, hipGetLastError());
-                hipLaunchKernelGGL(k_bd_reset_copy, dim3(E), dim3(256), 0, st, h->P, h->D, h->B, h->Q, mask, info);
-                HIPCHK(h, hipGetLastError());
-                // closes the running episodes of the mask and takes the new episode's snapshot (start position, box areas / centroids) from the reset state
-                hipLaunchKernelGGL(k_task_metrics, dim3((E + 255) / 256), dim3(256), 0, st, h->P, h->B, h->D, h->Q, 1, mask, (const unsigned char *)nullptr);
-                HIPCHK(h, hipGetLastError());
-            }
-        }
-        if (h->timing) HIPCHK(h, hipEventRecord(e1, st));
-        if (raster && obs) {
-            hipLaunchKernelGGL(k_bd_observe, dim3(E), dim3(BDO_THREADS), h->bd_obs_lds, st, h->P, h->D, h->B, h->Q, mask, obs);
+    if (int rc = bd_finish(h, Bx, st, out)) return rc;
+    if (side != st) HIPCHK(h, hipStreamWaitEvent(st, h->ev_join, 0));
+    return obs ? bd_observe(h, Bx, st, nullptr, obs) : BP_OK;
+}
+static int bd_physics(bp_handle *h, const BdParams &Bx, hipStream_t s)
+{
+    if (h->damp) hipLaunchKernelGGL(k_bd_physics_damp, dim3(h->num_envs), dim3(64), h->lds_bytes, s, h->P, h->D, Bx, h->Q);
+    else hipLaunchKernelGGL(k_bd_physics, dim3(h->num_envs), dim3(64), h->lds_bytes, s, h->P, h->D, Bx, h->Q);
+    HIPCHK(h, hipGetLastError());
+    return BP_OK;
+}
+// Two-pass step: a launch of k_bd_physics lasts as long as its slowest env, and the slowest are single wavefronts inside the reference's own 10 001-step loops
+// (DESIGN.md 4c).  Pass 0 gives every env `bd_budget` sim steps; the envs that are done -- all but a handful -- go through the tail on the caller's stream while
+// pass 1 carries the others to their end on a third stream, followed by the same kernels for that group.  Results are those of the single pass (the loop state
+// travels through Q.rs_*, bodies and arbiters through the ordinary store / load of a step boundary).  Returns with both groups joined on `st`.
+static int bd_step_two_pass(bp_handle *h, hipStream_t st, const StepOut &out, unsigned char *obs)
+{
+    const int E = h->num_envs;
+    BdParams B0 = h->B, B1 = h->B, Bs0 = h->B, Bs1 = h->B;
+    B0.budget = h->bd_budget; B0.pass = 0; B1.pass = 1; Bs0.sel_want = 0; Bs1.sel_want = 1;
+    if (int rc = bd_physics(h, B0, st)) return rc;
+    HIPCHK(h, hipEventRecord(h->ev_fork, st));
+    // group 1 (unfinished): third stream, its tail on that stream alone
+    HIPCHK(h, hipStreamWaitEvent(h->st_aux2, h->ev_fork, 0));
+    if (!h->damp && h->B.cycle_skip > 0) {
+        // the envs that stopped inside execute_robot_path: the kernel with the recurrence test (a robot pushing against a wall is over after a
+        // handful of sim steps there); then the others -- the reference's own until-still loops -- on the lean kernel
+        // (side by side on two streams: an env that pushes boxes through a long path is neither)
+        BdParams B1p = B1, B1s = B1;
+        B1p.resume_sel = 1; B1s.resume_sel = 2;
+        HIPCHK(h, hipStreamWaitEvent(h->st_aux3, h->ev_fork, 0));
+        hipLaunchKernelGGL(k_bd_physics_resume, dim3(E), dim3(64), h->lds_bytes, h->st_aux3, h->P, h->D, B1p, h->Q);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipEventRecord(h->ev_join3, h->st_aux3));
+        hipLaunchKernelGGL(k_bd_physics, dim3(E), dim3(64), h->lds_bytes, h->st_aux2, h->P, h->D, B1s, h->Q);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipStreamWaitEvent(h->st_aux2, h->ev_join3, 0));
+        HIPCHK(h, hipGetLastError());   // (the check that ends either arm, as bd_physics does in the other)
+    } else if (int rc = bd_physics(h, B1, h->st_aux2)) return rc;
+    if (int rc = bd_tail(h, Bs1, h->st_aux2, h->st_aux2, out, obs)) return rc;
+    HIPCHK(h, hipEventRecord(h->ev_join2, h->st_aux2));
+    // group 0 (done in pass 0): the caller's stream, the robot map beside the finish kernel as in the one-pass step
+    if (int rc = bd_tail(h, Bs0, st, h->st_aux, out, obs)) return rc;
+    HIPCHK(h, hipStreamWaitEvent(st, h->ev_join2, 0));
+    return BP_OK;
+}
+// Asynchronous step (bp_bd_step_async / bp_bd_async_drain, DESIGN.md "Asynchronous step"): idle envs are planned and started, busy ones resumed, each runs at
+// most `as.budget` sim steps; the envs whose env step ended (group byte 0) go through the tail exactly as in the one-pass step.
+// (Dispatch order: h->D.order is what the last lock-step step left, or none -- any permutation serves.)
+static int bd_step_slice(bp_handle *h, int mode, const double *actions, hipStream_t st, const StepOut &out, unsigned char *obs, const AsyncArgs &as)
+{
+    const int E = h->num_envs;
+    if (int rc = bd_side_streams(h, false)) return rc;
+    const int epoch = ++h->as_epoch;
+    BdParams Bp = h->B, Bl = h->B, Bt = h->B;
+    Bp.pass = Bl.pass = (mode == MODE_ASYNC) ? 2 : 3;
+    Bp.budget = Bl.budget = (mode == MODE_ASYNC) ? as.budget : 0;
+    Bp.resume_sel = 1; Bl.resume_sel = 2; Bt.sel_want = 0;
+    if (mode == MODE_ASYNC) {
+        hipLaunchKernelGGL(k_bd_plan_async, dim3(E), dim3(64), h->bd_lds, st, h->P, h->D, h->B, h->Q, actions);
+        HIPCHK(h, hipGetLastError());
+    }
+    // first the busy envs that stopped inside execute_robot_path (the kernel with the recurrence test), then every other env on the lean kernel
+    if (h->B.cycle_skip > 0) {
+        hipLaunchKernelGGL(k_bd_slice_resume, dim3(E), dim3(64), h->lds_bytes, st, h->P, h->D, Bp, h->Q, as.ready, as.slices, epoch);
+        HIPCHK(h, hipGetLastError());
+    } else Bl.resume_sel = 0;
+    hipLaunchKernelGGL(k_bd_slice, dim3(E), dim3(64), h->lds_bytes, st, h->P, h->D, Bl, h->Q, as.ready, as.slices, epoch);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(h->ev_fork, st));
+    if (int rc = bd_tail(h, Bt, st, h->st_aux, out, nullptr)) return rc;
+    // episode metrics: only the envs that emitted a transition in this call are accounted
+    hipLaunchKernelGGL(k_task_metrics, dim3((E + 255) / 256), dim3(256), 0, st, h->P, h->B, h->D, h->Q, 0, (const unsigned char *)nullptr, (const unsigned char *)as.ready);
+    HIPCHK(h, hipGetLastError());
+    return obs ? bd_observe(h, Bt, st, nullptr, obs) : BP_OK;   // only the envs that emitted a transition get a new observation
+}
+// A launch on a box-delivery / area-clearing handle.  e1, e2: the timing events of launch(), null without timing.
+static int launch_box(bp_handle *h, int mode, const double *actions, const unsigned char *mask, const StepOut &out, hipStream_t st, bool physics, bool raster,
+                      const AsyncArgs *as, hipEvent_t e1, hipEvent_t e2)
+{
+    const int E = h->num_envs;
+    unsigned char *obs = raster ? out.obs : nullptr;   // the observation still to enqueue
+    if (physics && mode == MODE_STEP) {
+        if (h->steps_done) {
+            hipLaunchKernelGGL(k_make_order, dim3(1), dim3(1024), 0, st, (const unsigned *)h->D.e_cost, h->order_buf, E, (unsigned *)nullptr);
             HIPCHK(h, hipGetLastError());
+            h->D.order = h->order_buf;
         }
-        if (h->timing) HIPCHK(h, hipEventRecord(e2, st));
-        return BP_OK;
+        h->steps_done = true;
+        hipLaunchKernelGGL(k_bd_plan, dim3(E), dim3(64), h->bd_lds, st, h->P, h->D, h->B, h->Q, actions);
+        HIPCHK(h, hipGetLastError());
+        if (int rc = bd_side_streams(h, true)) return rc;
+        if (h->bd_budget > 0) {
+            if (int rc = bd_step_two_pass(h, st, out, obs)) return rc;
+            obs = nullptr;   // both groups' observations are on their way
+        } else {
+            if (int rc = bd_physics(h, h->B, st)) return rc;
+            HIPCHK(h, hipEventRecord(h->ev_fork, st));
+            if (int rc = bd_tail(h, h->B, st, h->st_aux, out, nullptr)) return rc;
+        }
+        // episode metrics of the step (TaskDrivenMetric): both groups' finish kernels have joined the caller's stream
+        hipLaunchKernelGGL(k_task_metrics, dim3((E + 255) / 256), dim3(256), 0, st, h->P, h->B, h->D, h->Q, 0, (const unsigned char *)nullptr, (const unsigned char *)nullptr);
+        HIPCHK(h, hipGetLastError());
+    } else if (physics && (mode == MODE_ASYNC || mode == MODE_DRAIN)) {
+        if (int rc = bd_step_slice(h, mode, actions, st, out, obs, *as)) return rc;
+        obs = nullptr;
+    } else if (physics) {
+        hipLaunchKernelGGL(k_reset_copy, dim3(E), dim3(256), 0, st, h->P, h->D, mask, (double *)nullptr);
+        HIPCHK(h, hipGetLastError());
+        hipLaunchKernelGGL(k_bd_reset_copy, dim3(E), dim3(256), 0, st, h->P, h->D, h->B, h->Q, mask, out.info);
+        HIPCHK(h, hipGetLastError());
+        // closes the running episodes of the mask and takes the new episode's snapshot (start position, box areas / centroids) from the reset state
+        hipLaunchKernelGGL(k_task_metrics, dim3((E + 255) / 256), dim3(256), 0, st, h->P, h->B, h->D, h->Q, 1, mask, (const unsigned char *)nullptr);
+        HIPCHK(h, hipGetLastError());
     }
+    // (existing behaviour: in the two-pass and the asynchronous mode the observation is enqueued before e1, so the timers count it as physics)
+    if (e1) HIPCHK(h, hipEventRecord(e1, st));
+    if (obs) { if (int rc = bd_observe(h, h->B, st, mask, obs)) return rc; }
+    if (e2) HIPCHK(h, hipEventRecord(e2, st));
+    return BP_OK;
+}
+// A launch on a ship-ice / maze handle.
+static int launch_rigid(bp_handle *h, int mode, const double *actions, const unsigned char *mask, const StepOut &out, hipStream_t st, bool physics, bool raster,
+                        hipEvent_t e1, hipEvent_t e2)
+{
+    unsigned char *obs = out.obs, *term = out.term, *trunc = out.trunc;
+    double *reward = out.reward, *info = out.info;
     if (physics) {
         if (mode == MODE_STEP && h->steps_done) { // heaviest-first dispatch order from the previous step's per-env cycles
             hipLaunchKernelGGL(k_make_order, dim3(1), dim3(1024), 0, st, (const unsigned *)h->D.e_cost, h->order_buf, h->num_envs, h->D.sq_thr);
@@ -1174,6 +1174,31 @@ static int launch(bp_handle *h, int mode, const double *actions, const unsigned 
     if (h->timing) HIPCHK(h, hipEventRecord(e2, st));
     return BP_OK;
 }
+// Every kernel of one call of the entry points below.  With timing on, the call takes an event triple: e0 here, e1 between physics and observation, e2 at the end.
+static int launch(bp_handle *h, int mode, const double *actions, const unsigned char *mask, const StepOut &out, hipStream_t st, bool physics, bool raster,
+                  const AsyncArgs *as = nullptr)
+{
+    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
+    if (h->timing) {
+        if (h->ev_used + 3 > h->ev.size()) {
+            for (int k = 0; k < 3; k++) { hipEvent_t e; HIPCHK(h, hipEventCreate(&e)); h->ev.push_back(e); }
+        }
+        e0 = h->ev[h->ev_used]; e1 = h->ev[h->ev_used + 1]; e2 = h->ev[h->ev_used + 2];
+        h->ev_used += 3;
+        HIPCHK(h, hipEventRecord(e0, st));
+    }
+    if (h->P.env_kind == BP_ENV_BOX) return launch_box(h, mode, actions, mask, out, st, physics, raster, as, e1, e2);
+    return launch_rigid(h, mode, actions, mask, out, st, physics, raster, e1, e2);
+}
+// The reset kernels for the envs of `mask` (null: all).  Resets are not part of the per-step kernel timing.
+static int launch_reset_untimed(bp_handle *h, const unsigned char *mask, unsigned char *obs, double *info, hipStream_t st)
+{
+    const bool save = h->timing;
+    h->timing = false;
+    const int rc = launch(h, MODE_RESET, nullptr, mask, StepOut{obs, nullptr, nullptr, nullptr, info}, st, true, true);
+    h->timing = save;
+    return rc;
+}
 
 int bp_reset(bp_handle *h, const uint8_t *env_mask, uint8_t *obs, double *info, void *stream)
 {
@@ -1186,10 +1211,7 @@ int bp_reset(bp_handle *h, const uint8_t *env_mask, uint8_t *obs, double *info, 
         hipLaunchKernelGGL(k_bd_async_cancel, dim3((h->num_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->Q, env_mask, h->num_envs);
         HIPCHK(h, hipGetLastError());
     }
-    const bool save = h->timing;
-    h->timing = false; // resets are not part of the per-step kernel timing
-    const int rc = launch(h, MODE_RESET, nullptr, env_mask, obs, nullptr, nullptr, nullptr, info, (hipStream_t)stream, true, true);
-    h->timing = save;
+    const int rc = launch_reset_untimed(h, env_mask, obs, info, (hipStream_t)stream);
     if (rc == BP_OK) h->was_reset = true;
     if (rc == BP_OK && env_mask == nullptr) { h->async_open = false; h->q_batch = 0; }   // (an open ready queue is discarded with the slice)
     return rc;
@@ -1202,7 +1224,7 @@ int bp_step(bp_handle *h, const double *actions, uint8_t *obs, double *reward, u
     if (!h->loaded || !h->was_reset) return fail(h, BP_ESTATE, "bp_step before bp_load_scenarios/bp_reset");
     if (h->async_open) return fail(h, BP_ESTATE, "bp_step while an asynchronous slice is open (bp_bd_async_drain or a reset of all envs closes it)");
     BP_DEVICE(h);
-    return launch(h, MODE_STEP, actions, nullptr, obs, reward, terminated, truncated, info, (hipStream_t)stream, true, true);
+    return launch(h, MODE_STEP, actions, nullptr, StepOut{obs, reward, terminated, truncated, info}, (hipStream_t)stream, true, true);
 }
 
 int bp_step_physics(bp_handle *h, const double *actions, double *reward, uint8_t *terminated, uint8_t *truncated, double *info,
@@ -1212,7 +1234,7 @@ int bp_step_physics(bp_handle *h, const double *actions, double *reward, uint8_t
     if (!h->loaded || !h->was_reset) return fail(h, BP_ESTATE, "bp_step_physics before bp_load_scenarios/bp_reset");
     if (h->async_open) return fail(h, BP_ESTATE, "bp_step_physics while an asynchronous slice is open (bp_bd_async_drain or a reset of all envs closes it)");
     BP_DEVICE(h);
-    return launch(h, MODE_STEP, actions, nullptr, nullptr, reward, terminated, truncated, info, (hipStream_t)stream, true, false);
+    return launch(h, MODE_STEP, actions, nullptr, StepOut{nullptr, reward, terminated, truncated, info}, (hipStream_t)stream, true, false);
 }
 
 // ---- asynchronous step of box-delivery / area-clearing (DESIGN.md "Asynchronous step") ----
@@ -1224,6 +1246,27 @@ static int async_ready(bp_handle *h, const char *what)
     return BP_OK;
 }
 
+// Opens the slice, if none is open.  The flag is set before anything of the call is enqueued: should the call fail part-way, envs may already be busy, and the
+// handle must refuse bp_step / bp_save_state until a drain or a reset of all envs.
+static int slice_open(bp_handle *h, bool clear_unfin, hipStream_t st)
+{
+    if (!h->async_open) {
+        if (clear_unfin) HIPCHK(h, hipMemsetAsync(h->Q.unfin, 0, (size_t)h->num_envs, st));
+        if (h->as_epoch > 0x7FFF0000) {   // (serial numbers start over long before they wrap)
+            HIPCHK(h, hipMemsetAsync(h->Q.rs_i, 0, sizeof(int) * 16 * (size_t)h->num_envs, st));
+            h->as_epoch = 0;
+        }
+    }
+    h->async_open = true;
+    return BP_OK;
+}
+// The drain: the busy envs run to the end of their env steps with no budget; idle envs, and the held ones of a ready queue, emit nothing.
+static int launch_drain(bp_handle *h, const StepOut &out, unsigned char *ready, int *slices, hipStream_t st)
+{
+    const AsyncArgs as = {0, ready, slices};
+    return launch(h, MODE_DRAIN, nullptr, nullptr, out, st, true, true, &as);
+}
+
 int bp_bd_step_async(bp_handle *h, const double *actions, int32_t budget, uint8_t *obs, double *reward, uint8_t *terminated, uint8_t *truncated,
                      double *info, uint8_t *ready, int32_t *slices, void *stream)
 {
@@ -1232,19 +1275,10 @@ int bp_bd_step_async(bp_handle *h, const double *actions, int32_t budget, uint8_
     if (budget < 1) return fail(h, BP_EINVAL, "bp_bd_step_async: budget < 1 sim step");
     if (h->q_batch > 0) return fail(h, BP_ESTATE, "bp_bd_step_async while a ready queue is open (bp_bd_queue_recv steps the envs; bp_bd_queue_close or a reset of all envs closes it)");
     BP_DEVICE(h);
-    if (!h->async_open) {
-        // every env is idle.  The lock-step second pass never clears the group byte, and a drain leaves 2 in it: clear on opening
-        HIPCHK(h, hipMemsetAsync(h->Q.unfin, 0, (size_t)h->num_envs, (hipStream_t)stream));
-        if (h->as_epoch > 0x7FFF0000) {   // (serial numbers start over long before they wrap)
-            HIPCHK(h, hipMemsetAsync(h->Q.rs_i, 0, sizeof(int) * 16 * (size_t)h->num_envs, (hipStream_t)stream));
-            h->as_epoch = 0;
-        }
-    }
-    // open before anything of the call is enqueued: should the call fail part-way, envs may already be busy, and the handle must refuse bp_step / bp_save_state
-    // until a drain or a reset of all envs
-    h->async_open = true;
+    // every env is idle on opening.  The lock-step second pass never clears the group byte, and a drain leaves 2 in it: clear
+    if (int rc = slice_open(h, true, (hipStream_t)stream)) return rc;
     const AsyncArgs as = {budget, ready, slices};
-    return launch(h, MODE_ASYNC, actions, nullptr, obs, reward, terminated, truncated, info, (hipStream_t)stream, true, true, &as);
+    return launch(h, MODE_ASYNC, actions, nullptr, StepOut{obs, reward, terminated, truncated, info}, (hipStream_t)stream, true, true, &as);
 }
 
 int bp_bd_async_drain(bp_handle *h, uint8_t *obs, double *reward, uint8_t *terminated, uint8_t *truncated, double *info, uint8_t *ready,
@@ -1258,8 +1292,7 @@ int bp_bd_async_drain(bp_handle *h, uint8_t *obs, double *reward, uint8_t *termi
         HIPCHK(h, hipMemsetAsync(ready, 0, (size_t)h->num_envs, (hipStream_t)stream));
         return BP_OK;
     }
-    const AsyncArgs as = {0, ready, slices};
-    const int rc = launch(h, MODE_DRAIN, nullptr, nullptr, obs, reward, terminated, truncated, info, (hipStream_t)stream, true, true, &as);
+    const int rc = launch_drain(h, StepOut{obs, reward, terminated, truncated, info}, ready, slices, (hipStream_t)stream);
     if (rc == BP_OK) h->async_open = false;
     return rc;
 }
@@ -1299,12 +1332,8 @@ int bp_bd_queue_open(bp_handle *h, int32_t batch, void *stream)
     HIPCHK(h, hipMemsetAsync(h->q.hdr, 0, sizeof(int) * 4, st));
     HIPCHK(h, hipMemsetAsync(h->q.where, 0, (size_t)E, st));
     HIPCHK(h, hipMemsetAsync(h->q.actions, 0, sizeof(double) * 2 * (size_t)E, st));
-    if (h->as_epoch > 0x7FFF0000) {   // (serial numbers start over long before they wrap, as in bp_bd_step_async)
-        HIPCHK(h, hipMemsetAsync(h->Q.rs_i, 0, sizeof(int) * 16 * (size_t)E, st));
-        h->as_epoch = 0;
-    }
-    // open before anything is enqueued (as bp_bd_step_async): should a launch fail, the handle refuses bp_step / bp_save_state until a reset of all envs
-    h->async_open = true;
+    // no clear of the group bytes here: the enqueue kernel below writes every env's (held)
+    if (int rc = slice_open(h, false, st)) return rc;
     h->q_batch = batch;
     // every env becomes held and is queued with its current (reset) observation as a fresh row, in env-id order
     hipLaunchKernelGGL(k_bdq_enqueue, dim3(1), dim3(BDQ_THREADS), 0, st, h->q, h->Q.unfin, (const unsigned char *)nullptr, E, 1);
@@ -1330,7 +1359,7 @@ int bp_bd_queue_recv(bp_handle *h, int32_t budget, int32_t flags, uint8_t *obs_e
     const int E = h->num_envs, M = h->q_batch;
     // 1. one slice call exactly as bp_bd_step_async launches it; the envs take their actions from the queue's action rows (bp_bd_queue_send wrote them)
     const AsyncArgs as = {budget, emitted, slices_e};
-    if (int rc = launch(h, MODE_ASYNC, h->q.actions, nullptr, obs_e, reward_e, terminated_e, truncated_e, info_e, st, true, true, &as)) return rc;
+    if (int rc = launch(h, MODE_ASYNC, h->q.actions, nullptr, StepOut{obs_e, reward_e, terminated_e, truncated_e, info_e}, st, true, true, &as)) return rc;
     // 2. the envs that emitted are appended in ascending env id and become held; 3. up to M ids leave the head; 4. their rows are gathered
     hipLaunchKernelGGL(k_bdq_enqueue, dim3(1), dim3(BDQ_THREADS), 0, st, h->q, h->Q.unfin, (const unsigned char *)emitted, E, 0);
     HIPCHK(h, hipGetLastError());
@@ -1357,11 +1386,7 @@ int bp_bd_queue_send(bp_handle *h, const double *actions, const int32_t *ids, co
     HIPCHK(h, hipGetLastError());
     if (reset == nullptr) return BP_OK;
     // the reset rows: the masked reset of bp_reset with the mask the send kernel built (held envs are not busy: nothing to cancel), then their fresh rows
-    const bool save = h->timing;
-    h->timing = false;
-    const int rc = launch(h, MODE_RESET, nullptr, h->q.rmask, obs_e, nullptr, nullptr, nullptr, info_e, st, true, true);
-    h->timing = save;
-    if (rc) return rc;
+    if (int rc = launch_reset_untimed(h, h->q.rmask, obs_e, info_e, st)) return rc;
     hipLaunchKernelGGL(k_bdq_enqueue, dim3(1), dim3(BDQ_THREADS), 0, st, h->q, h->Q.unfin, (const unsigned char *)h->q.rmask, E, 1);
     HIPCHK(h, hipGetLastError());
     return BP_OK;
@@ -1373,9 +1398,7 @@ int bp_bd_queue_close(bp_handle *h, uint8_t *obs, double *reward, uint8_t *termi
     if (!h || !reward || !terminated || !truncated || !info || !ready || !slices) return BP_EINVAL;
     if (int rc = queue_ready(h, "bp_bd_queue_close")) return rc;
     BP_DEVICE(h);
-    // the drain: the busy envs run to the end of their env steps, held and idle envs emit nothing
-    const AsyncArgs as = {0, ready, slices};
-    if (int rc = launch(h, MODE_DRAIN, nullptr, nullptr, obs, reward, terminated, truncated, info, (hipStream_t)stream, true, true, &as)) return rc;
+    if (int rc = launch_drain(h, StepOut{obs, reward, terminated, truncated, info}, ready, slices, (hipStream_t)stream)) return rc;
     HIPCHK(h, hipMemsetAsync(h->Q.unfin, 0, (size_t)h->num_envs, (hipStream_t)stream));   // every env is idle, the queue is discarded
     h->async_open = false;
     h->q_batch = 0;
@@ -1389,7 +1412,7 @@ int bp_observe(bp_handle *h, const uint8_t *env_mask, uint8_t *obs, void *stream
     if (!h || !obs) return BP_EINVAL;
     if (!h->loaded || !h->was_reset) return fail(h, BP_ESTATE, "bp_observe before bp_load_scenarios/bp_reset");
     BP_DEVICE(h);
-    return launch(h, MODE_STEP, nullptr, env_mask, obs, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream, false, true);
+    return launch(h, MODE_STEP, nullptr, env_mask, StepOut{obs, nullptr, nullptr, nullptr, nullptr}, (hipStream_t)stream, false, true);
 }
 
 int bp_observe_global(bp_handle *h, const uint8_t *env_mask, uint8_t *obs, void *stream)
@@ -1982,7 +2005,6 @@ int bp_bd_load(bp_handle *h, int32_t T, int32_t nbox, const double *starts, cons
     std::vector<Shape> recepts(T);
     h->bd_map_of_trial.assign(T, 0);
     std::vector<std::vector<std::vector<P2>>> map_keys; // obstacle polygons of each distinct layout
-    int nphys_static = -1;
     for (int t = 0; t < T; t++) {
         std::vector<Shape> &bodies = trials[t];
         const double sx = starts[3 * t], sy = starts[3 * t + 1], sh = starts[3 * t + 2];
@@ -2006,7 +2028,7 @@ int bp_bd_load(bp_handle *h, int32_t T, int32_t nbox, const double *starts, cons
             bodies.push_back(s);
         }
         std::vector<std::vector<P2>> obstacles;
-        int nrec = 0, nst = 0;
+        int nrec = 0;
         for (int k = 0; k < ns; k++) {
             const size_t o = (size_t)t * ns + k;
             const int n = scount[o];
@@ -2024,11 +2046,9 @@ int bp_bd_load(bp_handle *h, int32_t T, int32_t nbox, const double *starts, cons
             s.kind = kind_of(3, 0, BODY_STATIC);
             bodies.push_back(s);
             obstacles.push_back(world_verts(s));
-            nst++;
         }
         if (cf.task == 0 && nrec != 1) return fail(h, BP_EINVAL, "exactly one receptacle polygon per trial is required");
         if (cf.task == 1 && nrec != 0) return fail(h, BP_EINVAL, "area-clearing has no receptacle polygon");
-        (void)nphys_static; (void)nst;
         int mi = -1;
         for (size_t m = 0; m < map_keys.size() && mi < 0; m++) {
             bool same = map_keys[m].size() == obstacles.size();
@@ -2171,13 +2191,7 @@ int bp_bd_load(bp_handle *h, int32_t T, int32_t nbox, const double *starts, cons
     if (h->damp) hipLaunchKernelGGL(k_bd_settle_damp, dim3(T), dim3(64), h->lds_bytes, 0, h->P, h->D, (const unsigned char *)nullptr, (double *)nullptr, 1);
     else hipLaunchKernelGGL(k_bd_settle, dim3(T), dim3(64), h->lds_bytes, 0, h->P, h->D, (const unsigned char *)nullptr, (double *)nullptr, 1);
     HIPCHK(h, hipGetLastError());
-    if (cf.task == 1)
-        hipLaunchKernelGGL(k_ac_finish, dim3(T), dim3(64), h->bd_lds, 0, h->P, h->D, h->B, h->Q, 1, 1, (double *)nullptr, (unsigned char *)nullptr,
-                           (unsigned char *)nullptr, (double *)nullptr);
-    else
-        hipLaunchKernelGGL(k_bd_finish, dim3(T), dim3(64), h->bd_lds, 0, h->P, h->D, h->B, h->Q, 1, 1, (double *)nullptr, (unsigned char *)nullptr,
-                           (unsigned char *)nullptr, (double *)nullptr);
-    HIPCHK(h, hipGetLastError());
+    if ((rc = bd_finish(h, h->B, 0, StepOut{}, 1))) return rc;
     hipLaunchKernelGGL(k_bd_robot_map, dim3(T), dim3(BDR_THREADS), h->bd_rmap_lds, 0, h->P, h->D, h->B, h->Q, 1);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipDeviceSynchronize());

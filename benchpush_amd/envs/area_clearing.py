@@ -38,51 +38,24 @@ class BatchedAreaClearingEnv(BatchedBoxDeliveryEnv):
     async_open / slices, the asynchronous step, are BatchedBoxDeliveryEnv's (the two tasks share the step kernels)."""
 
     render_task = "area_clearing"
-
+    _task_cfg = staticmethod(_ac_cfg)
+    _physics_params = staticmethod(area_clearing_physics_params)
+    _task_params = staticmethod(area_clearing_params)
+    _generate_trials = staticmethod(generate_trials)
+    _same_box_count = False
 
     def __init__(self, num_envs, cfg=None, trials=None, device="cuda:0", env_id_offset=0, num_trials=32, base_seed=0, bd_overrides=None):
-        if not torch.cuda.is_available():
-            raise _lib.BpError("BatchedAreaClearingEnv needs a ROCm GPU (torch.cuda.is_available() is False); no CPU fallback")
-        self.L = _lib.load()
-        self.cfg = _ac_cfg(cfg)
-        self.num_envs = int(num_envs)
-        self.device = torch.device(device)
-        self.params = area_clearing_physics_params(self.cfg)
-        self.bd_params = area_clearing_params(self.cfg)
-        if bd_overrides:   # constants of the reference that are not in its config (e.g. STEP_LIMIT): tests shorten them
-            self.bd_params.update(bd_overrides)
-        if trials is None:
-            trials = generate_trials(self.cfg, num_trials, base_seed)
-        self.trials = trials
-        nbox = len(trials[0]["boxes"])
-        self.nbox = nbox
-        self.bd_params["num_boxes"] = nbox
-        lay = env_layout(self.cfg)
-        self.goal_points = goal_points(self.cfg)
-        bcfg = _lib.make_bd_config(self.params, self.bd_params, self.cfg)
-        _lib.fill_area_geometry(bcfg, lay.boundary, lay.outer_boundary, self.cfg.agent.footprint_vertices, self.goal_points)
-        bcfg.distance_scale_max = self.bd_params["distance_scale_max"]
-        self.h = C.c_void_p()
-        dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        _lib.check(self.L, None, self.L.bp_bd_create(C.byref(bcfg), self.num_envs, int(env_id_offset), dev_index, C.byref(self.h)), "bp_bd_create")
-        c = lambda a, dt: np.ascontiguousarray(a, dt)
-        p = lambda a: a.ctypes.data_as(C.c_void_p)
-        starts = c(np.stack([t["start"] for t in trials]), np.float64)
-        boxes = c(np.stack([t["boxes"] for t in trials]), np.float64)
-        sv = c(np.stack([t["statics"][0] for t in trials]), np.float64)
-        sc = c(np.stack([t["statics"][1] for t in trials]), np.int32)
-        sp = c(np.stack([t["statics"][2] for t in trials]), np.float64)
-        sr = c(np.stack([t["statics"][3] for t in trials]), np.float64)
-        st = c(np.stack([t["statics"][4] for t in trials]), np.int32)
-        _lib.check(self.L, self.h, self.L.bp_bd_load(self.h, len(trials), nbox, p(starts), p(boxes), sv.shape[1], p(sv), p(sc), p(sp), p(sr), p(st)), "bp_bd_load")
-        self._alloc_io()
-        lp = self.L.bp_obs_height(self.h)
-        self.obs_shape = (lp, lp, 4)
-        self.obs = torch.zeros((self.num_envs,) + self.obs_shape, dtype=torch.uint8, device=self.device)
-        self.action_dim = 2 if self.cfg.agent.action_type == "velocity" else 1
-        self._actions = torch.zeros(self.num_envs * self.action_dim, dtype=torch.float64, device=self.device)
+        super().__init__(num_envs, cfg, trials, device, env_id_offset, num_trials, base_seed, bd_overrides)
         self.target_speed = float(self.cfg.controller.target_speed)     # area_clearing.py:196-209: what a 'velocity' action is scaled by
         self.max_yaw_rate_step = (np.pi / 2) / 15
+
+    def _bd_config(self):
+        lay = env_layout(self.cfg)
+        self.goal_points = goal_points(self.cfg)
+        bcfg = super()._bd_config()
+        _lib.fill_area_geometry(bcfg, lay.boundary, lay.outer_boundary, self.cfg.agent.footprint_vertices, self.goal_points)
+        bcfg.distance_scale_max = self.bd_params["distance_scale_max"]
+        return bcfg
 
     ASYNC_BUDGET = 3000   # the best of the measured sweep for this task (profiles/async/README.md: its env steps have no stragglers, so slicing only adds launches)
 

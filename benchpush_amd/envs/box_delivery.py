@@ -34,33 +34,45 @@ def _bd_cfg(cfg):
     return c
 
 
+def _out_ptrs(v):
+    """The five output pointers of the library's step calls, from an env's [E, ...] tensors or an AsyncQueue's [M, ...] ones."""
+    return _ptr(v.obs), _ptr(v.reward), _ptr(v.terminated), _ptr(v.truncated), _ptr(v.info)
+
+
 class BatchedBoxDeliveryEnv(BatchedShipIceEnv):
     """E independent box-delivery environments on one GPU: reset(mask) / step(actions) with device tensors."""
 
     render_task = "box_delivery"
+    # what differs between the two tasks: BatchedAreaClearingEnv overrides these and _bd_config, and passes its base_seed as `seed`
+    _task_cfg = staticmethod(_bd_cfg)
+    _physics_params = staticmethod(box_delivery_physics_params)
+    _task_params = staticmethod(box_delivery_params)
+    _generate_trials = staticmethod(generate_trials)
+    _same_box_count = True   # all trials must hold the same number of boxes
 
+    def _bd_config(self):
+        return _lib.make_bd_config(self.params, self.bd_params, self.cfg)
 
     def __init__(self, num_envs, cfg=None, trials=None, device="cuda:0", env_id_offset=0, num_trials=32, seed=None, bd_overrides=None):
         if not torch.cuda.is_available():
-            raise _lib.BpError("BatchedBoxDeliveryEnv needs a ROCm GPU (torch.cuda.is_available() is False); no CPU fallback")
+            raise _lib.BpError("%s needs a ROCm GPU (torch.cuda.is_available() is False); no CPU fallback" % type(self).__name__)
         self.L = _lib.load()
-        self.cfg = _bd_cfg(cfg)
+        self.cfg = self._task_cfg(cfg)
         self.num_envs = int(num_envs)
         self.device = torch.device(device)
-        self.params = box_delivery_physics_params(self.cfg)
-        self.bd_params = box_delivery_params(self.cfg)
+        self.params = self._physics_params(self.cfg)
+        self.bd_params = self._task_params(self.cfg)
         if bd_overrides:   # constants of the reference that are not in its config (e.g. STEP_LIMIT, box_delivery_env.py:62): tests shorten them
             self.bd_params.update(bd_overrides)
         if trials is None:
-            trials = generate_trials(self.cfg, num_trials, seed)
+            trials = self._generate_trials(self.cfg, num_trials, seed)
         self.trials = trials
-        nbox = len(trials[0]["boxes"])
+        self.nbox = nbox = len(trials[0]["boxes"])
         ns = max(len(t["statics"][1]) for t in trials)
-        if any(len(t["boxes"]) != nbox for t in trials):
+        if self._same_box_count and any(len(t["boxes"]) != nbox for t in trials):
             raise ValueError("all trials must hold the same number of boxes")
         self.bd_params["num_boxes"] = nbox
-        self.nbox = nbox
-        bcfg = _lib.make_bd_config(self.params, self.bd_params, self.cfg)
+        bcfg = self._bd_config()
         self.h = C.c_void_p()
         dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
         _lib.check(self.L, None, self.L.bp_bd_create(C.byref(bcfg), self.num_envs, int(env_id_offset), dev_index, C.byref(self.h)), "bp_bd_create")
@@ -88,8 +100,7 @@ class BatchedBoxDeliveryEnv(BatchedShipIceEnv):
     def step(self, actions):
         """actions: [E] heading in [-1, 1] / position index, or [E, 2] = (linear, angular) speed for 'velocity'."""
         self._actions.copy_(actions.reshape(-1).to(self.device), non_blocking=True)
-        _lib.check(self.L, self.h, self.L.bp_step(self.h, _ptr(self._actions), _ptr(self.obs), _ptr(self.reward), _ptr(self.terminated),
-                                                 _ptr(self.truncated), _ptr(self.info), self._stream()), "bp_step")
+        _lib.check(self.L, self.h, self.L.bp_step(self.h, _ptr(self._actions), *_out_ptrs(self), self._stream()), "bp_step")
         return self.obs, self.reward, self.terminated, self.truncated, self.info
 
     # -- asynchronous step (DESIGN.md "Asynchronous step") -------------------------------------------------
@@ -127,16 +138,15 @@ class BatchedBoxDeliveryEnv(BatchedShipIceEnv):
             raise _lib.BpError("step_async failed: BP_EINVAL (-1) actions must be a real tensor of %d elements" % self._actions.numel())
         ready, slices = self._async_io()   # (a config with sim.damping != 0 is refused by the library, before it launches anything)
         self._actions.copy_(actions.reshape(-1).to(self.device), non_blocking=True)
-        _lib.check(self.L, self.h, self.L.bp_bd_step_async(self.h, _ptr(self._actions), budget, _ptr(self.obs), _ptr(self.reward), _ptr(self.terminated),
-                                                           _ptr(self.truncated), _ptr(self.info), _ptr(ready), _ptr(slices), self._stream()), "bp_bd_step_async")
+        _lib.check(self.L, self.h, self.L.bp_bd_step_async(self.h, _ptr(self._actions), budget, *_out_ptrs(self), _ptr(ready), _ptr(slices), self._stream()),
+                   "bp_bd_step_async")
         return self.obs, self.reward, self.terminated, self.truncated, self.info, ready
 
     def drain(self):
         """Runs the busy envs, and only those, to the end of their env steps (no budget) and closes the slice; returns the six-tuple of step_async with `ready`
         marking the envs it finished.  Idle envs do nothing and emit nothing.  Afterwards step(), save_state, restore_state and clone_envs work again."""
         ready, slices = self._async_io()
-        _lib.check(self.L, self.h, self.L.bp_bd_async_drain(self.h, _ptr(self.obs), _ptr(self.reward), _ptr(self.terminated), _ptr(self.truncated),
-                                                            _ptr(self.info), _ptr(ready), _ptr(slices), self._stream()), "bp_bd_async_drain")
+        _lib.check(self.L, self.h, self.L.bp_bd_async_drain(self.h, *_out_ptrs(self), _ptr(ready), _ptr(slices), self._stream()), "bp_bd_async_drain")
         return self.obs, self.reward, self.terminated, self.truncated, self.info, ready
 
     def async_queue(self, batch_size, budget=None):
@@ -231,10 +241,8 @@ class AsyncQueue:
 
     def _recv_once(self, flags):
         v = self.env
-        _lib.check(v.L, v.h, v.L.bp_bd_queue_recv(v.h, self.budget, flags, _ptr(v.obs), _ptr(v.reward), _ptr(v.terminated), _ptr(v.truncated), _ptr(v.info),
-                                                  _ptr(self.emitted), _ptr(v._slices), _ptr(self.ids), _ptr(self.obs), _ptr(self.reward),
-                                                  _ptr(self.terminated), _ptr(self.truncated), _ptr(self.info), _ptr(self.slices), _ptr(self.counts),
-                                                  v._stream()), "bp_bd_queue_recv")
+        _lib.check(v.L, v.h, v.L.bp_bd_queue_recv(v.h, self.budget, flags, *_out_ptrs(v), _ptr(self.emitted), _ptr(v._slices), _ptr(self.ids),
+                                                  *_out_ptrs(self), _ptr(self.slices), _ptr(self.counts), v._stream()), "bp_bd_queue_recv")
         self._calls += 1
         self._counts_sum += self.counts
 
@@ -279,8 +287,7 @@ class AsyncQueue:
         [E] rows.  Afterwards every env is idle and step(), save_state and the rest work again."""
         v = self.env
         ready, slices = v._async_io()
-        _lib.check(v.L, v.h, v.L.bp_bd_queue_close(v.h, _ptr(v.obs), _ptr(v.reward), _ptr(v.terminated), _ptr(v.truncated), _ptr(v.info), _ptr(ready),
-                                                   _ptr(slices), v._stream()), "bp_bd_queue_close")
+        _lib.check(v.L, v.h, v.L.bp_bd_queue_close(v.h, *_out_ptrs(v), _ptr(ready), _ptr(slices), v._stream()), "bp_bd_queue_close")
         return v.obs, v.reward, v.terminated, v.truncated, v.info, ready
 
     def stats(self):
