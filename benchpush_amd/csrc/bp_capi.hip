@@ -29,6 +29,18 @@
 #include "bp_asyncq.hpp"
 #include "bp_replay.hpp"
 
+// The kernels of a ship-ice / maze handle, one per role, chosen once at load (rigid_kernels): the 8-vertex maze instantiations, the generic pair of a
+// handle with damping (no scheduler), or the ship-ice ones.
+typedef void (*StepKernel)(const DevParams, const DevPtrs, const double *, double *, unsigned char *, unsigned char *, double *);
+typedef void (*ResidentKernel)(const DevParams *, const DevPtrs *, const double *, double *, unsigned char *, unsigned char *, double *);
+typedef void (*ResetKernel)(const DevParams, const DevPtrs, const unsigned char *, double *, const int);
+struct RigidKernels {
+    StepKernel step = nullptr;          // one workgroup per env
+    StepKernel sched = nullptr;         // dispatcher-driven scheduled launch, and its completion launch
+    ResidentKernel resident = nullptr;  // scheduled launch on resident wavefronts (of a pairing launch: k_physics_step_schedr)
+    ResetKernel reset = nullptr;        // settles the templates at load, re-settles in reset() (bp_handle::resettle)
+};
+
 struct bp_handle {
     bp_config cfg;
     int num_envs = 0;
@@ -40,8 +52,9 @@ struct bp_handle {
     int *order_buf = nullptr;
     bool steps_done = false;
     bool resettle = false; // true: reset() re-runs the settle sub-steps instead of copying the settled template
-    bool maze8 = false;    // maze whose hulls all have <= 8 vertices: kernels instantiated with 8-vertex loops
     bool damp = false;     // bp_config.damping_pow != 0: k_physics_step_damp / k_physics_reset_damp (generic vertex loops, no scheduler)
+    RigidKernels k;                 // ship-ice / maze: the kernel of each role
+    BpLaunchPolicy pol = {};        // ship-ice / maze: the load-time policy of (num_envs, num_cus), bp_policy.hpp; the BP_* variables override its fields in the loader
     int pair_mode = 0;              // two envs per wavefront (bp_physics_pair.hpp): 1 = fixed pairs for the whole step (k_physics_step_pair), 2 = inside the scheduler
     int pair_resident = 0;          // > 0: pairing launches run k_physics_step_schedr with this many resident workgroups (BP_PAIR_RESIDENT)
     int sched_persist = 0;          // > 0: the scheduled launch is k_physics_step_schedl with this many resident workgroups (BP_SCHED_PERSIST)
@@ -53,8 +66,6 @@ struct bp_handle {
     unsigned launches = 0;
     int num_cus = 0;                // multiProcessorCount of the handle's device
     hipStream_t st_aux = nullptr;   // box-delivery / area-clearing: the robot's spfa map runs beside the finish kernel; ship-ice: the solo kernel of a pairing launch
-    std::vector<hipStream_t> st_parts;   // ship-ice: the scheduled launch split over several hardware queues (a measured variant; P.sq_parts is 1 since round 6)
-    std::vector<hipEvent_t> ev_parts;
     hipStream_t st_aux2 = nullptr;  // box-delivery / area-clearing: pass 1 of the two-pass step (the envs that ran out of pass 0's sim-step budget) and its tail kernels
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join2 = nullptr;
     hipStream_t st_aux3 = nullptr;  // ... pass 1's kernel with the recurrence test of execute_robot_path, beside the lean one
@@ -135,6 +146,22 @@ static int dalloc(bp_handle *h, T **p, size_t n, int fill_byte = 0)
     if (e != hipSuccess) return fail(h, BP_EHIP, std::string("hipMemset: ") + hipGetErrorString(e));
     h->allocs.push_back(q);
     *p = (T *)q;
+    return BP_OK;
+}
+
+// Host tables to the device.  Every table of a call is allocated (dalloc) before the first is filled: the order in which the loaders have always
+// issued these calls, and the traces of profiles/rigid_host pin it.
+struct DevTable { const void *src; size_t bytes; void *dev; };
+template <typename T>
+static DevTable dev_table(const std::vector<T> &v) { return {v.data(), sizeof(T) * v.size(), nullptr}; }
+static int upload_tables(bp_handle *h, DevTable *tab, int n)
+{
+    for (int k = 0; k < n; k++) {
+        unsigned char *q;
+        if (int rc = dalloc(h, &q, tab[k].bytes)) return rc;
+        tab[k].dev = q;
+    }
+    for (int k = 0; k < n; k++) HIPCHK(h, hipMemcpy(tab[k].dev, tab[k].src, tab[k].bytes, hipMemcpyHostToDevice));
     return BP_OK;
 }
 
@@ -332,8 +359,6 @@ int bp_destroy(bp_handle *h)
     if (h->st_aux2) { hipStreamSynchronize(h->st_aux2); hipStreamDestroy(h->st_aux2); }
     if (h->st_aux3) { hipStreamSynchronize(h->st_aux3); hipStreamDestroy(h->st_aux3); }
     if (h->ev_join3) hipEventDestroy(h->ev_join3);
-    for (hipStream_t s_ : h->st_parts) { hipStreamSynchronize(s_); hipStreamDestroy(s_); }
-    for (hipEvent_t e_ : h->ev_parts) hipEventDestroy(e_);
     if (h->ev_join2) hipEventDestroy(h->ev_join2);
     if (h->ev_fork) hipEventDestroy(h->ev_fork);
     if (h->ev_join) hipEventDestroy(h->ev_join);
@@ -343,84 +368,69 @@ int bp_destroy(bp_handle *h)
     return BP_OK;
 }
 
-// Common tail of the scenario loaders: SoA upload of the per-trial bodies, per-env state allocation, and one settle of
-// every trial into its reset template (state slot num_envs + t).
-static int upload_trials(bp_handle *h, const std::vector<std::vector<bpgeom::Shape>> &trials, bool settle = true)
+// ---- the scenario loader (upload_trials) as a sequence of steps ----------------------------------------------------------------------------------
+// Step 1: the per-trial bodies as SoA tables with nbcap slots per trial, and the scenario hash over them.
+struct TrialTables {
+    std::vector<int> nb, nv, kind;
+    std::vector<d2> lv, ln;
+    std::vector<double4> mass, pose, prop;
+};
+static int pack_trials(bp_handle *h, const std::vector<std::vector<bpgeom::Shape>> &trials, int nbcap, TrialTables &tt)
 {
     using namespace bpgeom;
     const int T = (int)trials.size();
-    int maxnb = 1;
-    for (const auto &b : trials) maxnb = std::max(maxnb, (int)b.size());
-    if (maxnb > 60000) return fail(h, BP_EINVAL, "too many bodies");
-    const int nbcap = (maxnb + 7) / 8 * 8;
-    h->nbcap = nbcap;
-    h->num_trials = T;
-    h->P.nbcap = nbcap;
-    h->P.mvcap = mvcap_for(nbcap);
-    h->P.num_trials = T;
-    h->lds_bytes = lds_bytes_for(nbcap, h->P.env_kind == BP_ENV_BOX);
-    if (h->lds_bytes > 160 * 1024) return fail(h, BP_EINVAL, "nb_cap too large for LDS");
-    // the candidate cache (LdsCtx::cc, bp_physics.hpp step 3) packs both body indices of a pair into BP_CC_IDX_BITS bits each
-    if (nbcap >= (1 << BP_CC_IDX_BITS)) return fail(h, BP_EINVAL, "nb_cap exceeds the candidate cache's body-index field (16384 bodies per env)");
-
-    std::vector<int> h_nb(T), h_nv((size_t)T * nbcap, 0), h_kind((size_t)T * nbcap, 0);
-    std::vector<d2> h_lv((size_t)T * nbcap * BP_MAXV), h_ln((size_t)T * nbcap * BP_MAXV);
-    std::vector<double4> h_mass((size_t)T * nbcap), h_pose((size_t)T * nbcap), h_prop((size_t)T * nbcap);
-    memset(h_lv.data(), 0, h_lv.size() * sizeof(d2));
-    memset(h_ln.data(), 0, h_ln.size() * sizeof(d2));
-    memset(h_mass.data(), 0, h_mass.size() * sizeof(double4));
-    memset(h_pose.data(), 0, h_pose.size() * sizeof(double4));
-    memset(h_prop.data(), 0, h_prop.size() * sizeof(double4));
+    tt.nb.assign(T, 0); tt.nv.assign((size_t)T * nbcap, 0); tt.kind.assign((size_t)T * nbcap, 0);
+    tt.lv.resize((size_t)T * nbcap * BP_MAXV); tt.ln.resize((size_t)T * nbcap * BP_MAXV);
+    tt.mass.resize((size_t)T * nbcap); tt.pose.resize((size_t)T * nbcap); tt.prop.resize((size_t)T * nbcap);
+    memset(tt.lv.data(), 0, tt.lv.size() * sizeof(d2));
+    memset(tt.ln.data(), 0, tt.ln.size() * sizeof(d2));
+    memset(tt.mass.data(), 0, tt.mass.size() * sizeof(double4));
+    memset(tt.pose.data(), 0, tt.pose.size() * sizeof(double4));
+    memset(tt.prop.data(), 0, tt.prop.size() * sizeof(double4));
     for (int t = 0; t < T; t++) {
-        h_nb[t] = (int)trials[t].size();
+        tt.nb[t] = (int)trials[t].size();
         for (int b = 0; b < (int)trials[t].size(); b++) {
             const Shape &s = trials[t][b];
             if ((int)s.verts.size() > BP_MAXV) return fail(h, BP_EINVAL, "hull exceeds BP_MAXV vertices");
             const size_t o = (size_t)t * nbcap + b;
-            h_nv[o] = (int)s.verts.size();
+            tt.nv[o] = (int)s.verts.size();
             for (int i = 0; i < (int)s.verts.size(); i++) {
-                h_lv[o * BP_MAXV + i].x = s.verts[i].x; h_lv[o * BP_MAXV + i].y = s.verts[i].y;
-                h_ln[o * BP_MAXV + i].x = s.normals[i].x; h_ln[o * BP_MAXV + i].y = s.normals[i].y;
+                tt.lv[o * BP_MAXV + i].x = s.verts[i].x; tt.lv[o * BP_MAXV + i].y = s.verts[i].y;
+                tt.ln[o * BP_MAXV + i].x = s.normals[i].x; tt.ln[o * BP_MAXV + i].y = s.normals[i].y;
             }
-            h_mass[o].x = s.m_inv; h_mass[o].y = s.i_inv; h_mass[o].z = s.cog.x; h_mass[o].w = s.cog.y;
-            h_pose[o].x = s.p.x; h_pose[o].y = s.p.y; h_pose[o].z = s.angle; h_pose[o].w = 0.0;
-            h_prop[o].x = s.radius; h_prop[o].y = s.e; h_prop[o].z = s.u; h_prop[o].w = 0.0;
-            h_kind[o] = s.kind;
+            tt.mass[o].x = s.m_inv; tt.mass[o].y = s.i_inv; tt.mass[o].z = s.cog.x; tt.mass[o].w = s.cog.y;
+            tt.pose[o].x = s.p.x; tt.pose[o].y = s.p.y; tt.pose[o].z = s.angle; tt.pose[o].w = 0.0;
+            tt.prop[o].x = s.radius; tt.prop[o].y = s.e; tt.prop[o].z = s.u; tt.prop[o].w = 0.0;
+            tt.kind[o] = s.kind;
         }
     }
-    {   // scenario hash of the state records' layout id: the tables exactly as they are uploaded
-        unsigned long long sh = h->scen_hash;
-        sh = bp_fnv1a(h_nb.data(), sizeof(int) * h_nb.size(), sh); sh = bp_fnv1a(h_nv.data(), sizeof(int) * h_nv.size(), sh);
-        sh = bp_fnv1a(h_kind.data(), sizeof(int) * h_kind.size(), sh);
-        sh = bp_fnv1a(h_lv.data(), sizeof(d2) * h_lv.size(), sh); sh = bp_fnv1a(h_ln.data(), sizeof(d2) * h_ln.size(), sh);
-        sh = bp_fnv1a(h_mass.data(), sizeof(double4) * h_mass.size(), sh); sh = bp_fnv1a(h_pose.data(), sizeof(double4) * h_pose.size(), sh);
-        sh = bp_fnv1a(h_prop.data(), sizeof(double4) * h_prop.size(), sh);
-        h->scen_hash = sh;
-    }
+    // scenario hash of the state records' layout id: the tables exactly as they are uploaded
+    unsigned long long sh = h->scen_hash;
+    sh = bp_fnv1a(tt.nb.data(), sizeof(int) * tt.nb.size(), sh); sh = bp_fnv1a(tt.nv.data(), sizeof(int) * tt.nv.size(), sh);
+    sh = bp_fnv1a(tt.kind.data(), sizeof(int) * tt.kind.size(), sh);
+    sh = bp_fnv1a(tt.lv.data(), sizeof(d2) * tt.lv.size(), sh); sh = bp_fnv1a(tt.ln.data(), sizeof(d2) * tt.ln.size(), sh);
+    sh = bp_fnv1a(tt.mass.data(), sizeof(double4) * tt.mass.size(), sh); sh = bp_fnv1a(tt.pose.data(), sizeof(double4) * tt.pose.size(), sh);
+    sh = bp_fnv1a(tt.prop.data(), sizeof(double4) * tt.prop.size(), sh);
+    h->scen_hash = sh;
+    return BP_OK;
+}
+// Step 2: the tables to the device (upload_tables)
+static int upload_trial_tables(bp_handle *h, const TrialTables &tt)
+{
+    DevTable tab[8] = {dev_table(tt.nb), dev_table(tt.nv), dev_table(tt.kind), dev_table(tt.lv), dev_table(tt.ln), dev_table(tt.mass), dev_table(tt.pose), dev_table(tt.prop)};
+    if (int rc = upload_tables(h, tab, 8)) return rc;
+    DevPtrs &D = h->D;
+    D.sc_nb = (const int *)tab[0].dev; D.sc_nv = (const int *)tab[1].dev; D.sc_kind = (const int *)tab[2].dev;
+    D.sc_lv = (const d2 *)tab[3].dev; D.sc_ln = (const d2 *)tab[4].dev;
+    D.sc_mass = (const double4 *)tab[5].dev; D.sc_pose = (const double4 *)tab[6].dev; D.sc_prop = (const double4 *)tab[7].dev;
+    return BP_OK;
+}
+// Step 3: per-env state for the E envs plus T settled reset templates (slot E + t = trial t)
+static int alloc_env_state(bp_handle *h, int T)
+{
     DevPtrs &D = h->D;
     int rc;
-    int *d_nb, *d_nv, *d_kind; d2 *d_lv, *d_ln; double4 *d_mass, *d_pose, *d_prop;
-    if ((rc = dalloc(h, &d_nb, T))) return rc;
-    if ((rc = dalloc(h, &d_nv, (size_t)T * nbcap))) return rc;
-    if ((rc = dalloc(h, &d_kind, (size_t)T * nbcap))) return rc;
-    if ((rc = dalloc(h, &d_lv, (size_t)T * nbcap * BP_MAXV))) return rc;
-    if ((rc = dalloc(h, &d_ln, (size_t)T * nbcap * BP_MAXV))) return rc;
-    if ((rc = dalloc(h, &d_mass, (size_t)T * nbcap))) return rc;
-    if ((rc = dalloc(h, &d_pose, (size_t)T * nbcap))) return rc;
-    if ((rc = dalloc(h, &d_prop, (size_t)T * nbcap))) return rc;
-    HIPCHK(h, hipMemcpy(d_nb, h_nb.data(), sizeof(int) * T, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(d_nv, h_nv.data(), sizeof(int) * h_nv.size(), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(d_kind, h_kind.data(), sizeof(int) * h_kind.size(), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(d_lv, h_lv.data(), sizeof(d2) * h_lv.size(), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(d_ln, h_ln.data(), sizeof(d2) * h_ln.size(), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(d_mass, h_mass.data(), sizeof(double4) * h_mass.size(), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(d_pose, h_pose.data(), sizeof(double4) * h_pose.size(), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(d_prop, h_prop.data(), sizeof(double4) * h_prop.size(), hipMemcpyHostToDevice));
-    D.sc_nb = d_nb; D.sc_nv = d_nv; D.sc_kind = d_kind; D.sc_lv = d_lv; D.sc_ln = d_ln; D.sc_mass = d_mass; D.sc_pose = d_pose;
-    D.sc_prop = d_prop;
-
-    // per-env state for the E envs plus T settled reset templates (slot E + t = trial t)
-    const size_t E = (size_t)h->num_envs + (size_t)T, EB = E * nbcap;
+    const size_t E = (size_t)h->num_envs + (size_t)T, EB = E * h->nbcap;
     if ((rc = dalloc(h, &D.e_trial, E))) return rc;
     if ((rc = dalloc(h, &D.e_episode, E, 0xFF))) return rc; // -1
     if ((rc = dalloc(h, &D.e_nb, E))) return rc;
@@ -467,6 +477,196 @@ static int upload_trials(bp_handle *h, const std::vector<std::vector<bpgeom::Sha
     if ((rc = dalloc(h, &D.clk, (size_t)16))) return rc;
     HIPCHK(h, hipMemset(D.clk, 0, 16 * sizeof(unsigned long long)));
     D.dbg = nullptr; D.dbg_env = -1; D.prof = nullptr;
+    return BP_OK;
+}
+// Step 4, the launch plan.  pair_limits / pair_resident_setup: two environments per wavefront inside the scheduler (pair_mode 2).
+static void pair_limits(bp_handle *h)
+{
+    // two environments per wavefront inside the scheduler: who starts alone, and when a half leaves its pair (pair_should_leave)
+    auto envint = [](const char *name, int dflt) { const char *v = getenv(name); return v ? atoi(v) : dflt; };
+    h->P.pair_mode = 2;
+    // (pace priorities stay on: +0.4 ... +0.9 % in pairing launches)
+    // Up to ~6 000 envs per GPU the launch is within a few per cent of the chain of its heaviest env: only envs that are light right now run
+    // paired (a medium env beside a mate would become the longest chain), and the eighth of the dispatch order that was heaviest in the previous
+    // step starts alone.  From ~7 000 envs the launch is throughput: every env starts in a pair and leaves it at 20 active arbiters or 40 work units per
+    // sub-step (same-box sweeps in profiles/r05_pair/ and profiles/r05_sched/pairing_limits_by_batch.txt; on the resident kernel, fresh / steady state:
+    // 6144 envs tight 294 k / 306 k against 294 k / 285 k, 7168 envs 300 k / 308 k against 314 k / 310 k, 8192 envs 303 k / 313 k against 323 k / 324 k).
+    BpLaunchPolicy &pol = h->pol;
+    if (pol.pair_mode != 2)   // (BP_PAIR=2 forced below the default regime)
+        bp_policy_pair_limits(pol, 2LL * h->num_envs < (long long)BP_POLICY_LOOSE_FROM_HALF_ROUNDS * pol.wave_slots, h->num_envs);
+    h->P.pair_solo = std::min(h->num_envs, std::max(0, envint("BP_PAIR_SOLO", pol.pair_solo)));
+    h->P.pp_max_keys = std::min(30, envint("BP_PP_KEYS", 26));
+    h->P.pp_max_slots = std::min(PP_NSLOT - 4, envint("BP_PP_SLOTS", 34));
+    h->P.pp_max_mv = std::min(PP_MVCAP - 4, envint("BP_PP_MV", 40));
+    h->P.pp_max_act = envint("BP_PP_ACT", pol.pp_max_act);
+    h->P.pp_max_work = envint("BP_PP_WORK", pol.pp_max_work);
+    h->P.pp_rate = envint("BP_PP_RATE", pol.pp_rate);
+    h->P.pp_snake = envint("BP_PP_SNAKE", 0);
+    h->P.pp_heavy_only = envint("BP_PP_HEAVY_ONLY", 0);
+}
+// (pairing launches have a resident kernel of their own, k_physics_step_schedr: the kernel that holds both step bodies INLINE lost 4 % at 8192 envs as a
+// resident loop -- 266 spilled VGPRs against 203)
+static int pair_resident_setup(bp_handle *h)
+{
+    HIPCHK(h, hipFuncSetAttribute((const void *)k_physics_step_schedr, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->sched_lds));
+    const int pr = getenv("BP_PAIR_RESIDENT") ? atoi(getenv("BP_PAIR_RESIDENT")) : 1;   // 0: the dispatcher-driven pair of kernels
+    if (pr > 0) {
+        h->pair_resident = std::min(h->num_envs, h->pol.wave_slots * pr);
+        if (!h->pd_buf) HIPCHK(h, hipMalloc(&h->pd_buf, sizeof(DevParams) + sizeof(DevPtrs)));
+        if (!getenv("BP_PAIR_RESIDENT")) { h->resident_auto = true; resident_acquire(h); h->device_shared = resident_device_shared(h); }
+    }
+    return BP_OK;
+}
+// Preemptive scheduler (k_physics_step_sched), the default step kernel of a ship-ice handle and of a maze handle with 8-vertex hulls: chunks of 40 sub-steps.
+// It pays while the launch is a few rounds of the wave slots (+14 % at 4096 envs; -1 % at 16 384, where the tail is amortised): BP_SCHED=<chunk> forces it,
+// BP_SCHED=0 selects the one-wave-per-env kernel.  h->pol and h->pair_mode are settled by the caller.
+static int sched_setup(bp_handle *h, bool maze)
+{
+    int rc;
+    // (with paired first tasks the scheduler is what lets an env leave its pair, so it stays on at every batch size: chunks of 100 sub-steps above 8192 envs)
+    int ch = h->pol.chunk ? h->pol.chunk : (h->pair_mode == 2 ? 100 : 0);
+    if (const char *ev = getenv("BP_SCHED")) ch = atoi(ev);
+    if (!(ch > 0 && (h->P.steps + ch - 1) / ch <= SQ_MAXLEV && h->num_envs < (1 << 24))) return BP_OK;
+    h->sched_chunk = ch;
+    h->P.sq_chunk = ch; h->P.sq_levels = (h->P.steps + ch - 1) / ch;
+    if (!maze) {
+        // Measured-and-lost scheduler variants (longest-remaining-first keys, hold, static class sets, the launch split over hardware queues: tools/experiments/README.md)
+        // are no longer load-time switches (round 6).  Their kernel code paths stay compiled -- taking them out of physics_body / sched_body moved the register allocation
+        // of k_physics_step_schedl and cost 1.0 % at 4096 envs, same box, both alternations (tools/experiments/r06_removed_scheduler_variants.diff) -- and are switched off here.
+        h->P.sq_hold = 0;
+        h->P.sq_lrpt = 0;
+        h->P.sq_bw = 9000;
+        h->P.sq_hyst = 1;
+        h->P.sq_floor = 150;
+        h->P.sq_cls = 0;
+        h->P.sq_parts = 1;
+        h->P.sq_part = 0;
+    }
+    // pace-based issue priorities (physics_body: pace_prio), per cent of the reference cost for priority 3: +1.5 ... +2.4 % at 4096 envs, flat from 100 to 130
+    // (maze, as for ship-ice: +1.6 % at 4096 envs)
+    h->P.sq_dynprio = getenv("BP_SCHED_DYNPRIO") ? atoi(getenv("BP_SCHED_DYNPRIO")) : 115;
+    h->P.sq_cap = h->num_envs; // an env's home XCD is where its first chunk ran: any share of the envs
+    int *d_items, *d_ctr; unsigned *d_carry; unsigned char *d_moved;
+    if ((rc = dalloc(h, &d_items, (size_t)SQ_NX * SQ_MAXLEV * h->P.sq_cap))) return rc;
+    if ((rc = dalloc(h, &d_ctr, (size_t)SQ_NX * (SQ_MAXLEV + 2) * 2))) return rc;
+    if ((rc = dalloc(h, &d_carry, (size_t)h->num_envs * 4))) return rc;
+    if ((rc = dalloc(h, &d_moved, (size_t)h->num_envs * h->nbcap))) return rc;
+    h->D.sq_items = d_items; h->D.sq_ctr = d_ctr; h->D.sq_carry = d_carry; h->D.sq_moved = d_moved;
+    int *d_done, *d_lev, *d_warn, *d_resc;
+    if ((rc = dalloc(h, &d_resc, (size_t)1 + SQ_RESCUE))) return rc;
+    h->D.sq_rescue = d_resc;
+    if ((rc = dalloc(h, &d_done, (size_t)h->num_envs))) return rc;
+    if ((rc = dalloc(h, &d_lev, (size_t)h->num_envs))) return rc;
+    if ((rc = dalloc(h, &d_warn, (size_t)2))) return rc;
+    HIPCHK(h, hipMemset(d_warn, 0, 2 * sizeof(int)));
+    h->D.sq_done = d_done; h->D.sq_lev = d_lev; h->D.sq_warn = d_warn;
+    unsigned *d_thr;
+    if ((rc = dalloc(h, &d_thr, (size_t)1))) return rc;
+    HIPCHK(h, hipMemset(d_thr, 0xFF, sizeof(unsigned)));
+    h->D.sq_thr = d_thr;
+    int *d_sub;
+    if ((rc = dalloc(h, &d_sub, (size_t)h->num_envs))) return rc;
+    h->D.sq_sub = d_sub;
+    if (!maze) {   // (cumulative pairing counters: a maze handle never pairs)
+        int *d_pst;
+        if ((rc = dalloc(h, &d_pst, (size_t)8))) return rc;
+        HIPCHK(h, hipMemset(d_pst, 0, 8 * sizeof(int)));
+        h->D.sq_pairstat = d_pst;
+    }
+#ifdef BP_DEBUG_PATHS   // fault injection lives in the diagnostic twin only: a stray variable in a job environment cannot disturb the product library
+    if (const char *ev2 = getenv("BP_SCHED_DEBUG_DROP")) h->P.sq_debug = atoi(ev2);
+#endif
+    if (h->pair_mode == 2) pair_limits(h);
+    // (the per-env kernels k_physics_step / k_physics_reset keep lds_bytes, for which their attribute was set by the loader)
+    h->sched_lds = h->pair_mode == 2 ? std::max(h->lds_bytes, (size_t)(2 * PL_HALF)) : h->lds_bytes;
+    h->P.sq_ymask = sched_yield_mask(h->P.pair_mode != 2, h->P.steps, h->P.sq_chunk);
+    if ((rc = sched_image_setup(h))) return rc;
+    if (maze) {
+        HIPCHK(h, hipFuncSetAttribute((const void *)k_physics_step_sched_maze, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->sched_lds));
+        HIPCHK(h, hipFuncSetAttribute((const void *)k_physics_step_schedl_maze, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->sched_lds));
+    } else {
+        HIPCHK(h, hipFuncSetAttribute((const void *)k_physics_step_sched, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->sched_lds));
+        HIPCHK(h, hipFuncSetAttribute((const void *)k_physics_step_schedp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->sched_lds));
+        HIPCHK(h, hipFuncSetAttribute((const void *)k_physics_step_schedl, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->sched_lds));
+    }
+    return h->P.pair_mode == 2 ? pair_resident_setup(h) : sched_persist_setup(h);
+}
+// The plan of a ship-ice handle without damping: pairing mode, then the scheduler.
+static int ship_plan(bp_handle *h, const std::vector<std::vector<bpgeom::Shape>> &trials)
+{
+    const int T = (int)trials.size(), nbcap = h->nbcap;
+    bool plain = true; // one kinematic shape (index 0), dynamic shapes without groups otherwise
+    for (int t = 0; t < T && plain; t++)
+        for (int b = 0; b < (int)trials[t].size(); b++) {
+            const int kd = trials[t][b].kind;
+            const int bt = (kd >> 16) & 3, grp = (kd >> 8) & 0xFF;
+            if (grp != 0 || bt != (b == 0 ? 1 : 0)) { plain = false; break; }
+        }
+    // two environments per wavefront: the half-wave LDS image is laid out for PP_NBCAP body slots, element offsets are 32-bit
+    const bool can_pair = plain && nbcap <= PP_NBCAP &&
+                          ((size_t)h->num_envs + (size_t)T) * (size_t)nbcap * BP_MAXV * sizeof(d2) < (size_t)0xFFFFFFFF &&   // 32-bit byte offsets (gA)
+                          ((size_t)h->num_envs + (size_t)T) * (size_t)nbcap * BP_KADJ * sizeof(unsigned long long) < (size_t)0xFFFFFFFF;
+    // Default: inside the scheduler (mode 2) from 5 120 envs per GPU up, where a launch is throughput (+3.7 % at 5 120, +12 % at 6 144, +19 % at 8 192 and
+    // +31 % at 16 384 env-steps/s over the resident solo scheduler, same box).  Below, the launch follows the chains of its heaviest envs and the scheduler's rotation, not the sum of the work: pairing
+    // the light envs saves a tenth of the wave-instructions and moves the launch by 0 ... +2.5 % at 4 096 envs (profiles/r05_pair/), -2 % at 2 048 --
+    // and the kernel that holds both step bodies runs the solo body 6 % slower -- so those handles keep the lean one-env-per-wavefront scheduler kernel.
+    // BP_PAIR=0 / 1 / 2 overrides.
+    if (int rc = device_cus(h)) return rc;
+    // regime boundaries in rounds of the device's wave slots, not in envs (bp_policy.hpp): pairing from 2.5 rounds, loose limits from 3.5, no scheduler
+    // without pairing above 4 -- 5 120 / 7 168 / 8 192 envs on the 256 CUs they were measured on
+    h->pol = bp_launch_policy(h->num_envs, h->num_cus, can_pair, false);
+    h->pair_mode = h->pol.pair_mode;
+    if (const char *evp = getenv("BP_PAIR")) h->pair_mode = can_pair ? atoi(evp) : 0;
+    if (h->pair_mode == 1) {
+        h->P.pair_mode = 1;
+        if (const char *evs = getenv("BP_PAIR_SNAKE")) h->P.pair_solo = atoi(evs);
+        HIPCHK(h, hipFuncSetAttribute((const void *)k_physics_step_pair, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * PL_HALF)));
+    }
+    if (plain) { if (int rc = sched_setup(h, false)) return rc; }
+    if (h->pair_mode == 2 && h->P.pair_mode != 2) h->pair_mode = 0;   // pairing inside the scheduler needs the scheduler
+    return BP_OK;
+}
+// The kernel of each role, chosen once (bp_handle::k).  maze8: a maze whose hulls all have <= 8 vertices, kernels instantiated with 8-vertex loops
+static RigidKernels rigid_kernels(const bp_handle *h, bool maze8)
+{
+    RigidKernels k;
+    if (h->damp) { k.step = k_physics_step_damp; k.reset = k_physics_reset_damp; }   // (no scheduler)
+    else if (maze8) { k.step = k_physics_step_maze; k.sched = k_physics_step_sched_maze; k.resident = k_physics_step_schedl_maze; k.reset = k_physics_reset_maze; }
+    else { k.step = k_physics_step; k.sched = k_physics_step_sched; k.resident = h->P.pair_mode == 2 ? k_physics_step_schedr : k_physics_step_schedl; k.reset = k_physics_reset; }
+    return k;
+}
+// Step 5: settle every trial once into its reset template (new space + bodies + 1000 sub-steps, ship_ice_env.py:109-220); reset() copies from these
+static int settle_templates(bp_handle *h)
+{
+    hipLaunchKernelGGL(h->k.reset, dim3(h->num_trials), dim3(64), h->lds_bytes, 0, h->P, h->D, (const unsigned char *)nullptr, (double *)nullptr, 1);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipDeviceSynchronize());
+    h->loaded = true;
+    return BP_OK;
+}
+// Common tail of the scenario loaders: SoA upload of the per-trial bodies, per-env state allocation, the launch plan, and one settle of
+// every trial into its reset template (state slot num_envs + t).  bp_bd_load passes settle = false: it plans and settles on its own.
+static int upload_trials(bp_handle *h, const std::vector<std::vector<bpgeom::Shape>> &trials, bool settle = true)
+{
+    const int T = (int)trials.size();
+    int maxnb = 1;
+    for (const auto &b : trials) maxnb = std::max(maxnb, (int)b.size());
+    if (maxnb > 60000) return fail(h, BP_EINVAL, "too many bodies");
+    const int nbcap = (maxnb + 7) / 8 * 8;
+    h->nbcap = nbcap;
+    h->num_trials = T;
+    h->P.nbcap = nbcap;
+    h->P.mvcap = mvcap_for(nbcap);
+    h->P.num_trials = T;
+    h->lds_bytes = lds_bytes_for(nbcap, h->P.env_kind == BP_ENV_BOX);
+    if (h->lds_bytes > 160 * 1024) return fail(h, BP_EINVAL, "nb_cap too large for LDS");
+    // the candidate cache (LdsCtx::cc, bp_physics.hpp step 3) packs both body indices of a pair into BP_CC_IDX_BITS bits each
+    if (nbcap >= (1 << BP_CC_IDX_BITS)) return fail(h, BP_EINVAL, "nb_cap exceeds the candidate cache's body-index field (16384 bodies per env)");
+    int rc;
+    TrialTables tt;
+    if ((rc = pack_trials(h, trials, nbcap, tt))) return rc;
+    if ((rc = upload_trial_tables(h, tt))) return rc;
+    if ((rc = alloc_env_state(h, T))) return rc;
     HIPCHK(h, hipDeviceSynchronize());
     HIPCHK(h, hipFuncSetAttribute((const void *)k_physics_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
     HIPCHK(h, hipFuncSetAttribute((const void *)k_physics_reset, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
@@ -475,190 +675,21 @@ static int upload_trials(bp_handle *h, const std::vector<std::vector<bpgeom::Sha
         // space.damping != 0: one generic pair of kernels for ship-ice and maze handles; settle every trial once with it
         HIPCHK(h, hipFuncSetAttribute((const void *)k_physics_step_damp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
         HIPCHK(h, hipFuncSetAttribute((const void *)k_physics_reset_damp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
-        if (!settle) return BP_OK;
-        hipLaunchKernelGGL(k_physics_reset_damp, dim3(T), dim3(64), h->lds_bytes, 0, h->P, h->D, (const unsigned char *)nullptr, (double *)nullptr, 1);
-        HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipDeviceSynchronize());
-        h->loaded = true;
-        return BP_OK;
+    } else if (h->P.env_kind == BP_ENV_SHIP_ICE && h->P.nkin == 1 && nbcap < 16384) {
+        if ((rc = ship_plan(h, trials))) return rc;
     }
-    if (h->P.env_kind == BP_ENV_SHIP_ICE && h->P.nkin == 1 && nbcap < 16384) {
-        bool plain = true; // one kinematic shape (index 0), dynamic shapes without groups otherwise
-        for (int t = 0; t < T && plain; t++)
-            for (int b = 0; b < (int)trials[t].size(); b++) {
-                const int kd = trials[t][b].kind;
-                const int bt = (kd >> 16) & 3, grp = (kd >> 8) & 0xFF;
-                if (grp != 0 || bt != (b == 0 ? 1 : 0)) { plain = false; break; }
-            }
-        // Preemptive scheduler (k_physics_step_sched), the default step kernel of a ship-ice handle: chunks of 40 sub-steps.  It pays while the launch
-        // is a few rounds of the wave slots (+14 % at 4096 envs; -1 % at 16 384, where the tail is amortised): BP_SCHED=<chunk> forces it, BP_SCHED=0
-        // selects the one-wave-per-env kernel.
-        // two environments per wavefront: the half-wave LDS image is laid out for PP_NBCAP body slots, element offsets are 32-bit
-        const bool can_pair = plain && nbcap <= PP_NBCAP &&
-                              ((size_t)h->num_envs + (size_t)T) * (size_t)nbcap * BP_MAXV * sizeof(d2) < (size_t)0xFFFFFFFF &&   // 32-bit byte offsets (gA)
-                              ((size_t)h->num_envs + (size_t)T) * (size_t)nbcap * BP_KADJ * sizeof(unsigned long long) < (size_t)0xFFFFFFFF;
-        // Default: inside the scheduler (mode 2) from 5 120 envs per GPU up, where a launch is throughput (+3.7 % at 5 120, +12 % at 6 144, +19 % at 8 192 and
-        // +31 % at 16 384 env-steps/s over the resident solo scheduler, same box).  Below, the launch follows the chains of its heaviest envs and the scheduler's rotation, not the sum of the work: pairing
-        // the light envs saves a tenth of the wave-instructions and moves the launch by 0 ... +2.5 % at 4 096 envs (profiles/r05_pair/), -2 % at 2 048 --
-        // and the kernel that holds both step bodies runs the solo body 6 % slower -- so those handles keep the lean one-env-per-wavefront scheduler kernel.
-        // BP_PAIR=0 / 1 / 2 overrides.
-        if ((rc = device_cus(h))) return rc;
-        // regime boundaries in rounds of the device's wave slots, not in envs (bp_policy.hpp): pairing from 2.5 rounds, loose limits from 3.5, no scheduler
-        // without pairing above 4 -- 5 120 / 7 168 / 8 192 envs on the 256 CUs they were measured on
-        const BpLaunchPolicy pol = bp_launch_policy(h->num_envs, h->num_cus, can_pair, false);
-        h->pair_mode = pol.pair_mode;
-        if (const char *evp = getenv("BP_PAIR")) h->pair_mode = can_pair ? atoi(evp) : 0;
-        if (h->pair_mode == 1) {
-            h->P.pair_mode = 1;
-            if (const char *evs = getenv("BP_PAIR_SNAKE")) h->P.pair_solo = atoi(evs);
-            HIPCHK(h, hipFuncSetAttribute((const void *)k_physics_step_pair, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * PL_HALF)));
-        }
-        // (with paired first tasks the scheduler is what lets an env leave its pair, so it stays on at every batch size: chunks of 100 sub-steps above 8192 envs)
-        int ch = pol.chunk ? pol.chunk : (h->pair_mode == 2 ? 100 : 0);
-        if (const char *ev = getenv("BP_SCHED")) ch = atoi(ev);
-        if (plain && ch > 0 && (h->P.steps + ch - 1) / ch <= SQ_MAXLEV && h->num_envs < (1 << 24)) {
-            h->sched_chunk = ch;
-            h->P.sq_chunk = ch; h->P.sq_levels = (h->P.steps + ch - 1) / ch;
-            // Measured-and-lost scheduler variants (longest-remaining-first keys, hold, static class sets, the launch split over hardware queues: tools/experiments/README.md)
-            // are no longer load-time switches (round 6).  Their kernel code paths stay compiled -- taking them out of physics_body / sched_body moved the register allocation
-            // of k_physics_step_schedl and cost 1.0 % at 4096 envs, same box, both alternations (tools/experiments/r06_removed_scheduler_variants.diff) -- and are switched off here.
-            h->P.sq_hold = 0;
-            h->P.sq_lrpt = 0;
-            h->P.sq_bw = 9000;
-            h->P.sq_hyst = 1;
-            h->P.sq_floor = 150;
-            // pace-based issue priorities (physics_body: pace_prio), per cent of the reference cost for priority 3: +1.5 ... +2.4 % at 4096 envs, flat from 100 to 130
-            h->P.sq_dynprio = getenv("BP_SCHED_DYNPRIO") ? atoi(getenv("BP_SCHED_DYNPRIO")) : 115;
-            h->P.sq_ymask = 0xFFFFFFFFu;   // (set below, once it is known whether the launch pairs)
-            h->P.sq_cls = 0;
-            h->P.sq_parts = 1;
-            h->P.sq_part = 0;
-            h->P.sq_cap = h->num_envs; // an env's home XCD is where its first chunk ran: any share of the envs
-            int *d_items, *d_ctr; unsigned *d_carry; unsigned char *d_moved;
-            if ((rc = dalloc(h, &d_items, (size_t)SQ_NX * SQ_MAXLEV * h->P.sq_cap))) return rc;
-            if ((rc = dalloc(h, &d_ctr, (size_t)SQ_NX * (SQ_MAXLEV + 2) * 2))) return rc;
-            if ((rc = dalloc(h, &d_carry, (size_t)h->num_envs * 4))) return rc;
-            if ((rc = dalloc(h, &d_moved, (size_t)h->num_envs * nbcap))) return rc;
-            h->D.sq_items = d_items; h->D.sq_ctr = d_ctr; h->D.sq_carry = d_carry; h->D.sq_moved = d_moved;
-            { int *d_done, *d_lev, *d_warn, *d_resc;
-              if ((rc = dalloc(h, &d_resc, (size_t)1 + SQ_RESCUE))) return rc;
-              h->D.sq_rescue = d_resc;
-              if ((rc = dalloc(h, &d_done, (size_t)h->num_envs))) return rc;
-              if ((rc = dalloc(h, &d_lev, (size_t)h->num_envs))) return rc;
-              if ((rc = dalloc(h, &d_warn, (size_t)2))) return rc;
-              HIPCHK(h, hipMemset(d_warn, 0, 2 * sizeof(int)));
-              h->D.sq_done = d_done; h->D.sq_lev = d_lev; h->D.sq_warn = d_warn;
-              unsigned *d_thr;
-              if ((rc = dalloc(h, &d_thr, (size_t)1))) return rc;
-              HIPCHK(h, hipMemset(d_thr, 0xFF, sizeof(unsigned)));
-              h->D.sq_thr = d_thr;
-              int *d_sub, *d_pst;
-              if ((rc = dalloc(h, &d_sub, (size_t)h->num_envs))) return rc;
-              if ((rc = dalloc(h, &d_pst, (size_t)8))) return rc;
-              HIPCHK(h, hipMemset(d_pst, 0, 8 * sizeof(int)));
-              h->D.sq_sub = d_sub; h->D.sq_pairstat = d_pst; }
-#ifdef BP_DEBUG_PATHS   // fault injection lives in the diagnostic twin only: a stray variable in a job environment cannot disturb the product library
-            if (const char *ev2 = getenv("BP_SCHED_DEBUG_DROP")) h->P.sq_debug = atoi(ev2);
-#endif
-            if (h->pair_mode == 2) {
-                // two environments per wavefront inside the scheduler: who starts alone, and when a half leaves its pair (pair_should_leave)
-                auto envint = [](const char *name, int dflt) { const char *v = getenv(name); return v ? atoi(v) : dflt; };
-                h->P.pair_mode = 2;
-                // (pace priorities stay on: +0.4 ... +0.9 % in pairing launches)
-                // Up to ~6 000 envs per GPU the launch is within a few per cent of the chain of its heaviest env: only envs that are light right now run
-                // paired (a medium env beside a mate would become the longest chain), and the eighth of the dispatch order that was heaviest in the previous
-                // step starts alone.  From ~7 000 envs the launch is throughput: every env starts in a pair and leaves it at 20 active arbiters or 40 work units per
-                // sub-step (same-box sweeps in profiles/r05_pair/ and profiles/r05_sched/pairing_limits_by_batch.txt; on the resident kernel, fresh / steady state:
-                // 6144 envs tight 294 k / 306 k against 294 k / 285 k, 7168 envs 300 k / 308 k against 314 k / 310 k, 8192 envs 303 k / 313 k against 323 k / 324 k).
-                const bool tight = pol.pair_mode == 2 ? pol.tight != 0 : 2LL * h->num_envs < (long long)BP_POLICY_LOOSE_FROM_HALF_ROUNDS * pol.wave_slots;   // (BP_PAIR=2 forced below the default regime)
-                h->P.pair_solo = std::min(h->num_envs, std::max(0, envint("BP_PAIR_SOLO", tight ? h->num_envs / 8 : 0)));
-                h->P.pp_max_keys = std::min(30, envint("BP_PP_KEYS", 26));
-                h->P.pp_max_slots = std::min(PP_NSLOT - 4, envint("BP_PP_SLOTS", 34));
-                h->P.pp_max_mv = std::min(PP_MVCAP - 4, envint("BP_PP_MV", 40));
-                h->P.pp_max_act = envint("BP_PP_ACT", tight ? 16 : 20);
-                h->P.pp_max_work = envint("BP_PP_WORK", tight ? 9 : 40);
-                h->P.pp_rate = envint("BP_PP_RATE", tight ? 70 : 200);
-                h->P.pp_snake = envint("BP_PP_SNAKE", 0);
-                h->P.pp_heavy_only = envint("BP_PP_HEAVY_ONLY", 0);
-            }
-            // (the per-env kernels k_physics_step / k_physics_reset keep lds_bytes, for which their attribute was set above)
-            h->sched_lds = h->pair_mode == 2 ? std::max(h->lds_bytes, (size_t)(2 * PL_HALF)) : h->lds_bytes;
-            HIPCHK(h, hipFuncSetAttribute((const void *)k_physics_step_sched, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->sched_lds));
-            HIPCHK(h, hipFuncSetAttribute((const void *)k_physics_step_schedp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->sched_lds));
-            HIPCHK(h, hipFuncSetAttribute((const void *)k_physics_step_schedl, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->sched_lds));
-            // (pairing launches have a resident kernel of their own, k_physics_step_schedr: the kernel that holds both step bodies INLINE lost 4 % at 8192 envs as a
-            // resident loop -- 266 spilled VGPRs against 203)
-            h->P.sq_ymask = sched_yield_mask(h->P.pair_mode != 2, h->P.steps, h->P.sq_chunk);
-            if ((rc = sched_image_setup(h))) return rc;
-            if (h->P.pair_mode != 2 && h->P.sq_parts == 1) { int rc2 = sched_persist_setup(h); if (rc2) return rc2; }
-            if (h->P.pair_mode == 2) {
-                HIPCHK(h, hipFuncSetAttribute((const void *)k_physics_step_schedr, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->sched_lds));
-                const int pr = getenv("BP_PAIR_RESIDENT") ? atoi(getenv("BP_PAIR_RESIDENT")) : 1;   // 0: the dispatcher-driven pair of kernels
-                if (pr > 0) {
-                    h->pair_resident = std::min(h->num_envs, pol.wave_slots * pr);
-                    if (!h->pd_buf) HIPCHK(h, hipMalloc(&h->pd_buf, sizeof(DevParams) + sizeof(DevPtrs)));
-                    if (!getenv("BP_PAIR_RESIDENT")) { h->resident_auto = true; resident_acquire(h); h->device_shared = resident_device_shared(h); }
-                }
-            }
-        }
-    }
-    if (h->pair_mode == 2 && h->P.pair_mode != 2) h->pair_mode = 0;   // pairing inside the scheduler needs the scheduler
     if (!settle) return BP_OK;
-    h->maze8 = (h->P.env_kind == BP_ENV_MAZE);
-    for (int v : h_nv) if (v > 8) h->maze8 = false;
-    if (h->maze8) {
+    bool maze8 = !h->damp && h->P.env_kind == BP_ENV_MAZE;
+    for (int v : tt.nv) if (v > 8) maze8 = false;
+    if (maze8) {
         if ((rc = device_cus(h))) return rc;
-        int ch = bp_launch_policy(h->num_envs, h->num_cus, false, true).chunk;
-        if (const char *ev = getenv("BP_SCHED")) ch = atoi(ev);
-        if (ch > 0 && (h->P.steps + ch - 1) / ch <= SQ_MAXLEV && h->num_envs < (1 << 24)) { // preemptive scheduler, as for ship-ice
-            h->sched_chunk = ch;
-            h->P.sq_chunk = ch; h->P.sq_levels = (h->P.steps + ch - 1) / ch; h->P.sq_cap = h->num_envs;
-            h->P.sq_dynprio = getenv("BP_SCHED_DYNPRIO") ? atoi(getenv("BP_SCHED_DYNPRIO")) : 115;   // pace priorities as for ship-ice: +1.6 % at 4096 envs
-            h->P.sq_ymask = sched_yield_mask(true, h->P.steps, h->P.sq_chunk);
-            int *d_items, *d_ctr; unsigned *d_carry; unsigned char *d_moved;
-            if ((rc = dalloc(h, &d_items, (size_t)SQ_NX * SQ_MAXLEV * h->P.sq_cap))) return rc;
-            if ((rc = dalloc(h, &d_ctr, (size_t)SQ_NX * (SQ_MAXLEV + 2) * 2))) return rc;
-            if ((rc = dalloc(h, &d_carry, (size_t)h->num_envs * 4))) return rc;
-            if ((rc = dalloc(h, &d_moved, (size_t)h->num_envs * nbcap))) return rc;
-            h->D.sq_items = d_items; h->D.sq_ctr = d_ctr; h->D.sq_carry = d_carry; h->D.sq_moved = d_moved;
-            { int *d_done, *d_lev, *d_warn, *d_resc;
-              if ((rc = dalloc(h, &d_resc, (size_t)1 + SQ_RESCUE))) return rc;
-              h->D.sq_rescue = d_resc;
-              if ((rc = dalloc(h, &d_done, (size_t)h->num_envs))) return rc;
-              if ((rc = dalloc(h, &d_lev, (size_t)h->num_envs))) return rc;
-              if ((rc = dalloc(h, &d_warn, (size_t)2))) return rc;
-              HIPCHK(h, hipMemset(d_warn, 0, 2 * sizeof(int)));
-              h->D.sq_done = d_done; h->D.sq_lev = d_lev; h->D.sq_warn = d_warn;
-              unsigned *d_thr;
-              if ((rc = dalloc(h, &d_thr, (size_t)1))) return rc;
-              HIPCHK(h, hipMemset(d_thr, 0xFF, sizeof(unsigned)));
-              h->D.sq_thr = d_thr;
-              int *d_sub;
-              if ((rc = dalloc(h, &d_sub, (size_t)h->num_envs))) return rc;
-              h->D.sq_sub = d_sub; }
-#ifdef BP_DEBUG_PATHS
-            if (const char *ev2 = getenv("BP_SCHED_DEBUG_DROP")) h->P.sq_debug = atoi(ev2);
-#endif
-            h->sched_lds = h->lds_bytes;
-            if ((rc = sched_image_setup(h))) return rc;
-            HIPCHK(h, hipFuncSetAttribute((const void *)k_physics_step_sched_maze, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
-            HIPCHK(h, hipFuncSetAttribute((const void *)k_physics_step_schedl_maze, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
-            if ((rc = sched_persist_setup(h))) return rc;
-        }
+        h->pol = bp_launch_policy(h->num_envs, h->num_cus, false, true);
+        if ((rc = sched_setup(h, true))) return rc;   // preemptive scheduler, as for ship-ice
         HIPCHK(h, hipFuncSetAttribute((const void *)k_physics_step_maze, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
         HIPCHK(h, hipFuncSetAttribute((const void *)k_physics_reset_maze, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
-        hipLaunchKernelGGL(k_physics_reset_maze, dim3(T), dim3(64), h->lds_bytes, 0, h->P, h->D, (const unsigned char *)nullptr, (double *)nullptr, 1);
-        HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipDeviceSynchronize());
-        h->loaded = true;
-        return BP_OK;
     }
-    // settle every trial once (new space + bodies + 1000 sub-steps, ship_ice_env.py:109-220); reset() copies from these
-    hipLaunchKernelGGL(k_physics_reset, dim3(T), dim3(64), h->lds_bytes, 0, h->P, h->D, (const unsigned char *)nullptr, (double *)nullptr, 1);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipDeviceSynchronize());
-    h->loaded = true;
-    return BP_OK;
+    h->k = rigid_kernels(h, maze8);
+    return settle_templates(h);
 }
 
 // State records: the segment table over this handle's arrays, its device copy and the layout id (bp_state.hpp).  Called once, at the end of every loader.
@@ -758,25 +789,20 @@ int bp_load_maze(bp_handle *h, int32_t T, int32_t nbox, const double *centres, i
     std::vector<unsigned char> wall;
     std::vector<double> norm;
     maze_maps(walls, nwalls, cf.wall_radius, cf.map_w, cf.map_h, h->P.grid_h, h->P.grid_w, cf.goal_x, cf.goal_y, wall, norm, h->goal_raw);
-    double *d_norm; unsigned char *d_wall;
     int rc;
-    if ((rc = dalloc(h, &d_norm, norm.size()))) return rc;
-    if ((rc = dalloc(h, &d_wall, wall.size()))) return rc;
-    HIPCHK(h, hipMemcpy(d_norm, norm.data(), sizeof(double) * norm.size(), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(d_wall, wall.data(), wall.size(), hipMemcpyHostToDevice));
-    h->D.dist_map = d_norm; h->D.wall_map = d_wall;
+    DevTable maps[2] = {dev_table(norm), dev_table(wall)};
+    if ((rc = upload_tables(h, maps, 2))) return rc;
+    h->D.dist_map = (const double *)maps[0].dev; h->D.wall_map = (const unsigned char *)maps[1].dev;
     {   // the observer's packed copy: sign = wall, magnitude = normalised distance (a wall cell's distance is exactly 1.0, never a zero)
         std::vector<double> packed(norm.size());
         for (size_t i = 0; i < norm.size(); i++) packed[i] = wall[i] ? -norm[i] : norm[i];
-        double *d_pk;
-        if ((rc = dalloc(h, &d_pk, packed.size()))) return rc;
-        HIPCHK(h, hipMemcpy(d_pk, packed.data(), sizeof(double) * packed.size(), hipMemcpyHostToDevice));
-        h->D.maze_obs_map = d_pk;
+        DevTable pk = dev_table(packed);
+        if ((rc = upload_tables(h, &pk, 1))) return rc;
+        h->D.maze_obs_map = (const double *)pk.dev;
     }
-    double *d_raw;
-    if ((rc = dalloc(h, &d_raw, h->goal_raw.size()))) return rc;
-    HIPCHK(h, hipMemcpy(d_raw, h->goal_raw.data(), sizeof(double) * h->goal_raw.size(), hipMemcpyHostToDevice));
-    h->D.goal_raw = d_raw;
+    DevTable raw = dev_table(h->goal_raw);
+    if ((rc = upload_tables(h, &raw, 1))) return rc;
+    h->D.goal_raw = (const double *)raw.dev;
     h->scen_hash = bp_fnv1a(wall.data(), wall.size(), h->scen_hash);
     h->scen_hash = bp_fnv1a(norm.data(), sizeof(double) * norm.size(), h->scen_hash);
     h->scen_hash = bp_fnv1a(h->goal_raw.data(), sizeof(double) * h->goal_raw.size(), h->scen_hash);
@@ -1062,26 +1088,17 @@ static int launch_rigid(bp_handle *h, int mode, const double *actions, const uns
             // resident launches only while this process has the device to itself (see resident_device_shared)
             if (h->resident_auto && (++h->launches & 63u) == 0) h->device_shared = resident_device_shared(h);
             const bool resident_ok = !(h->resident_auto && h->device_shared);
-            if (h->sched_persist && resident_ok) {
-                // resident wavefronts: one workgroup per wave slot for the whole launch; the launch constants go through device memory (see sched_resident)
+            // resident wavefronts: one workgroup per wave slot for the whole launch (sched_persist_setup); of a pairing launch: one kernel, the two step bodies as
+            // functions of their own (pair_resident_setup)
+            const int resident = !resident_ok ? 0 : h->P.pair_mode == 2 ? h->pair_resident : h->sched_persist;
+            if (resident > 0) {
+                // the launch constants go through device memory (see sched_resident)
                 DevParams *Pg = (DevParams *)h->pd_buf;
                 DevPtrs *Dg = (DevPtrs *)((char *)h->pd_buf + sizeof(DevParams));
                 hipLaunchKernelGGL(k_store_params, dim3(1), dim3(64), 0, st, h->P, h->D, Pg, Dg);
                 HIPCHK(h, hipGetLastError());
-                if (h->maze8)
-                    hipLaunchKernelGGL(k_physics_step_schedl_maze, dim3(h->sched_persist), dim3(64), h->sched_lds, st, Pg, Dg, actions, reward, term, trunc, info);
-                else
-                    hipLaunchKernelGGL(k_physics_step_schedl, dim3(h->sched_persist), dim3(64), h->sched_lds, st, Pg, Dg, actions, reward, term, trunc, info);
-            } else if (h->pair_resident > 0 && h->P.pair_mode == 2 && resident_ok) {
-                // a pairing launch on resident wavefronts: one kernel, the two step bodies as functions of their own (k_physics_step_schedr)
-                DevParams *Pg = (DevParams *)h->pd_buf;
-                DevPtrs *Dg = (DevPtrs *)((char *)h->pd_buf + sizeof(DevParams));
-                hipLaunchKernelGGL(k_store_params, dim3(1), dim3(64), 0, st, h->P, h->D, Pg, Dg);
-                HIPCHK(h, hipGetLastError());
-                hipLaunchKernelGGL(k_physics_step_schedr, dim3(h->pair_resident), dim3(64), h->sched_lds, st, Pg, Dg, actions, reward, term, trunc, info);
-            } else if (h->maze8)
-                hipLaunchKernelGGL(k_physics_step_sched_maze, dim3(h->num_envs * h->P.sq_levels), dim3(64), h->sched_lds, st, h->P, h->D, actions, reward, term, trunc, info);
-            else if (h->P.pair_mode == 2) {
+                hipLaunchKernelGGL(h->k.resident, dim3(resident), dim3(64), h->sched_lds, st, Pg, Dg, actions, reward, term, trunc, info);
+            } else if (h->P.pair_mode == 2) {
                 // (BP_PAIR_RESIDENT=0) a pairing launch as two kernels side by side: the envs that start alone on the lean solo code (second stream), everything else -- paired
                 // first tasks, the workgroups that serve the queues -- in the kernel that holds both step bodies
                 if (!h->st_aux) {
@@ -1099,27 +1116,8 @@ static int launch_rigid(bp_handle *h, int mode, const double *actions, const uns
                 hipLaunchKernelGGL(k_physics_step_schedp, dim3(h->num_envs * h->P.sq_levels), dim3(64), h->sched_lds, st, h->P, h->D, actions, reward, term, trunc, info);
                 HIPCHK(h, hipGetLastError());
                 if (h->P.pair_solo > 0) HIPCHK(h, hipStreamWaitEvent(st, h->ev_join, 0));
-            } else if (h->P.sq_parts > 1) {
-                // the scheduled launch as several kernels on several streams (hardware queues)
-                const int np = h->P.sq_parts;
-                if (h->st_parts.empty()) {
-                    for (int k = 0; k < 7; k++) { hipStream_t s_; HIPCHK(h, hipStreamCreateWithFlags(&s_, hipStreamNonBlocking)); h->st_parts.push_back(s_); }
-                    for (int k = 0; k < 8; k++) { hipEvent_t e_; HIPCHK(h, hipEventCreateWithFlags(&e_, hipEventDisableTiming)); h->ev_parts.push_back(e_); }
-                }
-                HIPCHK(h, hipEventRecord(h->ev_parts[7], st));
-                for (int k = 0; k < np; k++) {
-                    DevParams Pk = h->P;
-                    Pk.sq_part = k;
-                    hipStream_t sk = (k == 0) ? st : h->st_parts[k - 1];
-                    if (k > 0) HIPCHK(h, hipStreamWaitEvent(sk, h->ev_parts[7], 0));
-                    const int grid = (h->num_envs * h->P.sq_levels + np - 1) / np;
-                    hipLaunchKernelGGL(k_physics_step_sched, dim3(grid), dim3(64), h->sched_lds, sk, Pk, h->D, actions, reward, term, trunc, info);
-                    HIPCHK(h, hipGetLastError());
-                    if (k > 0) { HIPCHK(h, hipEventRecord(h->ev_parts[k - 1], sk)); }
-                }
-                for (int k = 1; k < np; k++) HIPCHK(h, hipStreamWaitEvent(st, h->ev_parts[k - 1], 0));
             } else
-                hipLaunchKernelGGL(k_physics_step_sched, dim3(h->num_envs * h->P.sq_levels), dim3(64), h->sched_lds, st, h->P, h->D, actions, reward, term, trunc, info);
+                hipLaunchKernelGGL(h->k.sched, dim3(h->num_envs * h->P.sq_levels), dim3(64), h->sched_lds, st, h->P, h->D, actions, reward, term, trunc, info);
             HIPCHK(h, hipGetLastError());
             // completion launch: workgroup b finishes the b-th env that the scheduled launch left unfinished (scheduler watchdog); normally all leave at once
 #ifdef BP_DEBUG_PATHS
@@ -1132,24 +1130,13 @@ static int launch_rigid(bp_handle *h, int mode, const double *actions, const uns
                 HIPCHK(h, hipGetLastError());
                 DevParams PC = h->P;
                 PC.sq_mode = 1;
-                if (h->maze8)
-                    hipLaunchKernelGGL(k_physics_step_sched_maze, dim3(std::min(h->num_envs, SQ_RESCUE)), dim3(64), h->sched_lds, st, PC, h->D, actions, reward, term, trunc, info);
-                else
-                    hipLaunchKernelGGL(k_physics_step_sched, dim3(std::min(h->num_envs, SQ_RESCUE)), dim3(64), h->sched_lds, st, PC, h->D, actions, reward, term, trunc, info);
+                hipLaunchKernelGGL(h->k.sched, dim3(std::min(h->num_envs, SQ_RESCUE)), dim3(64), h->sched_lds, st, PC, h->D, actions, reward, term, trunc, info);
             }
         }
-        else if (mode == MODE_STEP && h->damp)
-            hipLaunchKernelGGL(k_physics_step_damp, dim3(h->num_envs), dim3(64), h->lds_bytes, st, h->P, h->D, actions, reward, term, trunc, info);
-        else if (h->resettle && h->damp)
-            hipLaunchKernelGGL(k_physics_reset_damp, dim3(h->num_envs), dim3(64), h->lds_bytes, st, h->P, h->D, mask, info, 0);
-        else if (mode == MODE_STEP && h->maze8)
-            hipLaunchKernelGGL(k_physics_step_maze, dim3(h->num_envs), dim3(64), h->lds_bytes, st, h->P, h->D, actions, reward, term, trunc, info);
         else if (mode == MODE_STEP)
-            hipLaunchKernelGGL(k_physics_step, dim3(h->num_envs), dim3(64), h->lds_bytes, st, h->P, h->D, actions, reward, term, trunc, info);
-        else if (h->resettle && h->maze8)
-            hipLaunchKernelGGL(k_physics_reset_maze, dim3(h->num_envs), dim3(64), h->lds_bytes, st, h->P, h->D, mask, info, 0);
+            hipLaunchKernelGGL(h->k.step, dim3(h->num_envs), dim3(64), h->lds_bytes, st, h->P, h->D, actions, reward, term, trunc, info);
         else if (h->resettle)
-            hipLaunchKernelGGL(k_physics_reset, dim3(h->num_envs), dim3(64), h->lds_bytes, st, h->P, h->D, mask, info, 0);
+            hipLaunchKernelGGL(h->k.reset, dim3(h->num_envs), dim3(64), h->lds_bytes, st, h->P, h->D, mask, info, 0);
         else
             hipLaunchKernelGGL(k_reset_copy, dim3(h->num_envs), dim3(256), 0, st, h->P, h->D, mask, info);
         HIPCHK(h, hipGetLastError());
@@ -1158,10 +1145,8 @@ static int launch_rigid(bp_handle *h, int mode, const double *actions, const uns
             HIPCHK(h, hipGetLastError());
             h->cost_n++;
         }
-        if (h->P.env_kind == BP_ENV_SHIP_ICE || h->P.env_kind == BP_ENV_MAZE) {
-            hipLaunchKernelGGL(k_episode_metrics, dim3((h->num_envs + 255) / 256), dim3(256), 0, st, h->P, h->D, mode == MODE_STEP ? 0 : 1, mask);
-            HIPCHK(h, hipGetLastError());
-        }
+        hipLaunchKernelGGL(k_episode_metrics, dim3((h->num_envs + 255) / 256), dim3(256), 0, st, h->P, h->D, mode == MODE_STEP ? 0 : 1, mask);
+        HIPCHK(h, hipGetLastError());
     }
     if (h->timing) HIPCHK(h, hipEventRecord(e1, st));
     if (raster && obs) {

@@ -25,6 +25,17 @@ struct BpLaunchPolicy {
 #define BP_POLICY_LOOSE_FROM_HALF_ROUNDS 7
 #define BP_POLICY_SCHED_UPTO_HALF_ROUNDS 8
 
+// The pairing limits of a regime: who starts alone and when a half leaves its pair.  bp_launch_policy states its own regime with it, and so does the loader
+// when BP_PAIR=2 forces pairing on a handle that the default policy does not pair.
+static inline void bp_policy_pair_limits(BpLaunchPolicy &p, bool tight, int num_envs)
+{
+    p.tight = tight ? 1 : 0;
+    p.pair_solo = tight ? num_envs / 8 : 0;
+    p.pp_max_act = tight ? 16 : 20;
+    p.pp_max_work = tight ? 9 : 40;
+    p.pp_rate = tight ? 70 : 200;
+}
+
 static inline BpLaunchPolicy bp_launch_policy(int num_envs, int num_cus, bool can_pair, bool maze)
 {
     BpLaunchPolicy p{};
@@ -33,11 +44,7 @@ static inline BpLaunchPolicy bp_launch_policy(int num_envs, int num_cus, bool ca
     const bool pairing = !maze && can_pair && half_rounds2 >= (long long)BP_POLICY_PAIR_FROM_HALF_ROUNDS * p.wave_slots;
     p.pair_mode = pairing ? 2 : 0;
     // chain-bound pairing regime: up to 3.5 rounds the launch is within a few per cent of its heaviest env's chain
-    p.tight = pairing && half_rounds2 < (long long)BP_POLICY_LOOSE_FROM_HALF_ROUNDS * p.wave_slots ? 1 : 0;
-    p.pair_solo = p.tight ? num_envs / 8 : 0;
-    p.pp_max_act = p.tight ? 16 : 20;
-    p.pp_max_work = p.tight ? 9 : 40;
-    p.pp_rate = p.tight ? 70 : 200;
+    bp_policy_pair_limits(p, pairing && half_rounds2 < (long long)BP_POLICY_LOOSE_FROM_HALF_ROUNDS * p.wave_slots, num_envs);
     // the preemptive scheduler pays while a launch is a few rounds of the slots (its turns even out the finish); above four rounds the tail is
     // amortised, and only pairing launches keep it (it is what lets an env leave its pair) with long chunks
     const bool few_rounds = half_rounds2 <= (long long)BP_POLICY_SCHED_UPTO_HALF_ROUNDS * p.wave_slots;
