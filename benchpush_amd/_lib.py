@@ -20,23 +20,6 @@ INFO_KEYS = ["x", "y", "theta", "total_work", "work", "collision_reward", "scale
              "trial_success", "boundary_violated", "yaw_violated", "total_ke", "total_impulse", "n_post_solve",
              "n_contact_pts", "n_first_contact"]
 ERRORS = {0: "BP_OK", -1: "BP_EINVAL", -2: "BP_ENOMEM", -3: "BP_EHIP", -4: "BP_ENODEVICE", -5: "BP_ESTATE", -6: "BP_ECAPACITY"}
-EXPORTS = ["bp_abi_version", "bp_create", "bp_destroy", "bp_load_scenarios", "bp_load_maze", "bp_get_goal_map", "bp_reset", "bp_step", "bp_step_physics",
-           "bp_observe", "bp_observe_global", "bp_set_resettle", "bp_sizeof_config", "bp_get_world_polys", "bp_get_body_state", "bp_get_low_dim_obs", "bp_costmap_update", "bp_nb_cap", "bp_obs_height",
-           "bp_obs_width", "bp_get_num_bodies", "bp_check_errors", "bp_kernel_time_ms", "bp_enable_timing", "bp_get_step_cycles", "bp_set_step_cost_hint", "bp_sched_chunk", "bp_sched_resident", "bp_sched_warnings", "bp_get_clock_stamps", "bp_last_error",
-           "bp_bd_create", "bp_bd_load", "bp_bd_sizeof_config", "bp_bd_get_maps", "bp_bd_get_state",
-           "bp_get_episode_metrics", "bp_get_episode_history", "bp_start_uniform", "bp_debug_round2", "bp_debug_scramble_hints",
-           "bp_copy_rows_masked", "bp_pair_mode", "bp_get_pair_stats", "bp_bd_get_stragglers",
-           "bp_device_shared", "bp_launch_policy_query", "bp_bd_budget", "bp_get_cost_stats", "bp_bd_get_cycle_skips",
-           "bp_sizeof_render_args", "bp_sizeof_render_prim", "bp_set_render_table", "bp_render",
-           "bp_state_bytes", "bp_state_layout_id", "bp_save_state", "bp_load_state", "bp_clone_state", "bp_state_layout_query",
-           "bp_sizeof_swath_config", "bp_swath_cost",
-           "bp_sizeof_lattice_config", "bp_lattice_workspace_bytes", "bp_lattice_search",
-           "bp_sizeof_track_config", "bp_track_path",
-           "bp_sizeof_rrt_config", "bp_rrt_workspace_bytes", "bp_rrt_uniform", "bp_rrt_plan", "bp_sizeof_track_wp_config", "bp_track_waypoints",
-           "bp_sizeof_gtsp_config", "bp_gtsp_workspace_bytes", "bp_gtsp_plan", "bp_gtsp_track",
-           "bp_bd_step_async", "bp_bd_async_drain", "bp_bd_async_open", "bp_bd_get_episode_boxes", "bp_bd_get_completed", "bp_task_metric_row",
-           "bp_bd_queue_open", "bp_bd_queue_recv", "bp_bd_queue_send", "bp_bd_queue_close", "bp_bd_queue_batch",
-           "bp_sizeof_replay_desc", "bp_sizeof_replay_batch", "bp_replay_index", "bp_replay_observe", "bp_replay_record", "bp_replay_sample"]
 GTSP_OK, GTSP_NOTHING_TO_PUSH, GTSP_SKIPPED, GTSP_CAP, GTSP_INVALID = range(5)
 GTSP_STATUS_MASK, GTSP_FLAG_VANISHED, GTSP_FLAG_DEGENERATE = 0xFF, 0x100, 0x200   # status = code | flags
 GTSP_MAX_BOXES, GTSP_MAX_GOALS, GTSP_MAX_SLOTS = 12, 8, 64
@@ -137,6 +120,98 @@ class BpBdConfig(C.Structure):
                 ("wheel_verts", ((C.c_double * 2) * 4) * 4), ("bumper_verts", (C.c_double * 2) * 4), ("robot_mass", C.c_double)]
 
 
+def _abi():
+    """The C ABI as one table: name -> (restype, argtypes, group).  group None: every supported library has the symbol; otherwise the probe symbol of
+    the feature it came with -- a library without the probe (an older build loaded for a same-box comparison) goes without the whole group.
+    tests/test_host_cpu.py holds the table against the prototypes of include/benchpush_amd.h."""
+    from .render import RenderArgs, RenderPrim
+    P, I, vp, i32, i64, u64, f64 = C.POINTER, C.c_int, C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_double
+    step_out = [vp] * 5                                          # obs, reward, terminated, truncated, info
+    groups = {
+        None: {
+            "bp_abi_version": (i32, []), "bp_last_error": (C.c_char_p, [vp]),
+            "bp_create": (I, [P(BpConfig), i32, i64, i32, P(vp)]), "bp_destroy": (I, [vp]),
+            "bp_load_scenarios": (I, [vp, i32, i32, i32, vp, vp, vp, vp, vp]), "bp_load_maze": (I, [vp, i32, i32, vp, i32, vp, vp]),
+            "bp_get_goal_map": (I, [vp, vp, P(i32), P(i32)]),
+            "bp_reset": (I, [vp, vp, vp, vp, vp]), "bp_step": (I, [vp, vp] + step_out + [vp]), "bp_step_physics": (I, [vp, vp, vp, vp, vp, vp, vp]),
+            "bp_observe": (I, [vp, vp, vp, vp]), "bp_observe_global": (I, [vp, vp, vp, vp]), "bp_set_resettle": (I, [vp, i32]),
+            "bp_get_world_polys": (I, [vp, vp, vp, vp]), "bp_get_body_state": (I, [vp, vp, vp]), "bp_get_low_dim_obs": (I, [vp, vp, vp]),
+            "bp_costmap_update": (I, [vp, P(BpCostmapConfig), vp, f64, vp, vp]),
+            "bp_get_episode_metrics": (I, [vp, vp, vp, vp]), "bp_start_uniform": (f64, [u64, i64, i64]),
+            "bp_debug_round2": (I, [vp, vp, i32, vp]), "bp_copy_rows_masked": (I, [vp, vp, vp, vp, i64, i64, vp]),
+            "bp_nb_cap": (i32, [vp]), "bp_obs_height": (i32, [vp]), "bp_obs_width": (i32, [vp]),
+            "bp_get_num_bodies": (I, [vp, vp]), "bp_check_errors": (I, [vp, vp]),
+            "bp_kernel_time_ms": (I, [vp, P(f64), P(f64), P(i32)]), "bp_enable_timing": (I, [vp, i32]),
+            "bp_get_step_cycles": (I, [vp, vp]), "bp_set_step_cost_hint": (I, [vp, vp]),
+            "bp_sched_chunk": (i32, [vp]), "bp_sched_resident": (i32, [vp]), "bp_pair_mode": (i32, [vp]), "bp_get_pair_stats": (I, [vp, vp]),
+            "bp_bd_create": (I, [P(BpBdConfig), i32, i64, i32, P(vp)]), "bp_bd_load": (I, [vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
+            "bp_bd_get_maps": (I, [vp, i32, vp, vp, vp, vp, vp, vp]), "bp_bd_get_state": (I, [vp, vp, vp, vp]), "bp_bd_get_stragglers": (I, [vp, vp]),
+        },
+        "bp_get_episode_history": {"bp_get_episode_history": (I, [vp, vp, vp, vp, vp])},
+        "bp_debug_scramble_hints": {"bp_debug_scramble_hints": (I, [vp, u64, vp])},
+        "bp_device_shared": {   # ABI 11
+            "bp_device_shared": (i32, [vp]), "bp_bd_budget": (i32, [vp]), "bp_launch_policy_query": (I, [i32, i32, i32, i32, vp]),
+            "bp_get_cost_stats": (I, [vp, vp, i32, P(i32)])},
+        "bp_bd_get_cycle_skips": {"bp_bd_get_cycle_skips": (I, [vp, vp])},
+        "bp_get_clock_stamps": {"bp_get_clock_stamps": (I, [vp, vp])},
+        "bp_sched_warnings": {"bp_sched_warnings": (I, [vp, vp])},   # absent from libraries of ABI 6
+        "bp_bd_step_async": {   # asynchronous step
+            "bp_bd_step_async": (I, [vp, vp, i32] + step_out + [vp, vp, vp]), "bp_bd_async_drain": (I, [vp] + step_out + [vp, vp, vp]),
+            "bp_bd_async_open": (i32, [vp])},
+        "bp_bd_queue_open": {   # ready queue of the asynchronous step
+            "bp_bd_queue_open": (I, [vp, i32, vp]), "bp_bd_queue_recv": (I, [vp, i32, i32] + [vp] * 16), "bp_bd_queue_send": (I, [vp] * 7),
+            "bp_bd_queue_close": (I, [vp] * 9), "bp_bd_queue_batch": (i32, [vp])},
+        "bp_task_metric_row": {   # episode metrics of box handles
+            "bp_bd_get_episode_boxes": (I, [vp, vp, vp]), "bp_bd_get_completed": (I, [vp, vp]),
+            "bp_task_metric_row": (I, [i32, vp, vp, i32, vp, vp, f64, f64, f64, f64, f64, vp])},
+        "bp_render": {
+            "bp_set_render_table": (I, [vp, i32, i32, vp, vp, i32, vp]), "bp_render": (I, [vp, P(RenderArgs), vp, i32, vp, vp, vp, vp])},
+        "bp_save_state": {   # state records
+            "bp_state_bytes": (i64, [vp]), "bp_state_layout_id": (u64, [vp]), "bp_save_state": (I, [vp, vp, i32, vp, vp]),
+            "bp_load_state": (I, [vp, vp, i32, vp, i32, vp]), "bp_clone_state": (I, [vp, vp, vp, i32, i32, vp]),
+            "bp_state_layout_query": (I, [i32, i32, i32, i32, i32, vp, vp, vp, P(i64), P(u64)])},
+        "bp_swath_cost": {"bp_swath_cost": (I, [vp, P(BpSwathConfig)] + [vp] * 8)},
+        "bp_lattice_search": {
+            "bp_lattice_workspace_bytes": (i64, [P(BpLatticeConfig), i32]),
+            "bp_lattice_search": (I, [vp, P(BpLatticeConfig)] + [vp] * 10 + [i64] + [vp] * 7)},
+        "bp_track_path": {"bp_track_path": (I, [vp, P(BpTrackConfig), vp, i64] + [vp] * 8)},
+        "bp_rrt_plan": {   # batched RRT and its waypoint controller
+            "bp_rrt_workspace_bytes": (i64, [P(BpRrtConfig), i32]), "bp_rrt_uniform": (f64, [u64, i64, i32, i32, i32]),
+            "bp_rrt_plan": (I, [vp, P(BpRrtConfig), vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, i64] + [vp] * 6),
+            "bp_track_waypoints": (I, [vp, P(BpTrackWpConfig)] + [vp] * 7)},
+        "bp_gtsp_plan": {   # the GTSP push planner and its controller
+            "bp_gtsp_workspace_bytes": (i64, [P(BpGtspConfig), i32]),
+            "bp_gtsp_plan": (I, [vp, P(BpGtspConfig), vp, vp, vp, i32, i32, vp, vp, vp, i64] + [vp] * 10),
+            "bp_gtsp_track": (I, [vp, P(BpGtspConfig)] + [vp] * 9)},
+        "bp_replay_observe": {   # replay buffer on the ready queue
+            "bp_replay_index": (i64, [u64, i64, i32, i64]), "bp_replay_observe": (I, [P(BpReplayDesc)] + [vp] * 7 + [i32, i32, vp]),
+            "bp_replay_record": (I, [P(BpReplayDesc), vp, vp, vp, i32, vp]),
+            "bp_replay_sample": (I, [P(BpReplayDesc), i32, u64, P(BpReplayBatch), vp])},
+    }
+    # (sizeof function, the struct it measures, group, the error when the two disagree); the functions join their groups in the table
+    layouts = [("bp_sizeof_config", BpConfig, None, "bp_config layout mismatch between _lib.BpConfig and the library"),
+               ("bp_bd_sizeof_config", BpBdConfig, None, "bp_bd_config layout mismatch between _lib.BpBdConfig and the library"),
+               ("bp_sizeof_render_args", RenderArgs, "bp_render", "bp_render_args / bp_render_prim layout mismatch between benchpush_amd.render and the library"),
+               ("bp_sizeof_render_prim", RenderPrim, "bp_render", "bp_render_args / bp_render_prim layout mismatch between benchpush_amd.render and the library"),
+               ("bp_sizeof_swath_config", BpSwathConfig, "bp_swath_cost", "bp_swath_config layout mismatch between _lib.BpSwathConfig and the library"),
+               ("bp_sizeof_lattice_config", BpLatticeConfig, "bp_lattice_search", "bp_lattice_config layout mismatch between _lib.BpLatticeConfig and the library"),
+               ("bp_sizeof_track_config", BpTrackConfig, "bp_track_path", "bp_track_config layout mismatch between _lib.BpTrackConfig and the library"),
+               ("bp_sizeof_rrt_config", BpRrtConfig, "bp_rrt_plan", "bp_rrt_config / bp_track_wp_config layout mismatch between _lib and the library"),
+               ("bp_sizeof_track_wp_config", BpTrackWpConfig, "bp_rrt_plan", "bp_rrt_config / bp_track_wp_config layout mismatch between _lib and the library"),
+               ("bp_sizeof_gtsp_config", BpGtspConfig, "bp_gtsp_plan", "bp_gtsp_config layout mismatch between _lib.BpGtspConfig and the library"),
+               ("bp_sizeof_replay_desc", BpReplayDesc, "bp_replay_observe", "bp_replay_desc / bp_replay_batch layout mismatch between _lib and the library"),
+               ("bp_sizeof_replay_batch", BpReplayBatch, "bp_replay_observe", "bp_replay_desc / bp_replay_batch layout mismatch between _lib and the library")]
+    table = {name: decl + (group,) for group, fns in groups.items() for name, decl in fns.items()}
+    table.update((name, (i32, [], group)) for name, _, group, _ in layouts)
+    # entry points of the library that the header does not declare: the diagnostic twins' hooks (tools/, tests of the twins)
+    diagnostic = {"bp_debug_trace": (I, [vp, vp, i32], None), "bp_debug_prof": (I, [vp, vp], None)}
+    return table, diagnostic, [(name, struct, what) for name, struct, _, what in layouts]
+
+
+ABI, DIAGNOSTIC_ABI, LAYOUTS = _abi()
+EXPORTS = list(ABI)
+
+
 class BpError(RuntimeError):
     pass
 
@@ -160,155 +235,17 @@ def load():
     if os.environ.get("BP_PROF") == "1":  # diagnostic build with in-kernel phase timers (tools/prof_phases.py)
         path = os.environ.get("BP_PROF_LIB", LIB_PATH.replace(".so", "_prof.so"))
     L = C.CDLL(path)
-    vp = C.c_void_p
-    L.bp_abi_version.restype = C.c_int32
-    L.bp_sizeof_config.restype = C.c_int32
-    if L.bp_sizeof_config() != C.sizeof(BpConfig):
-        raise BpError("bp_config layout mismatch between _lib.BpConfig and the library")
-    L.bp_create.argtypes = [C.POINTER(BpConfig), C.c_int32, C.c_int64, C.c_int32, C.POINTER(vp)]
-    L.bp_destroy.argtypes = [vp]
-    L.bp_load_scenarios.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp]
-    L.bp_load_maze.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, vp, vp]
-    L.bp_get_goal_map.argtypes = [vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-    L.bp_reset.argtypes = [vp, vp, vp, vp, vp]
-    L.bp_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
-    L.bp_step_physics.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    L.bp_observe.argtypes = [vp, vp, vp, vp]
-    L.bp_observe_global.argtypes = [vp, vp, vp, vp]
-    L.bp_get_world_polys.argtypes = [vp, vp, vp, vp]
-    L.bp_get_body_state.argtypes = [vp, vp, vp]
-    L.bp_get_low_dim_obs.argtypes = [vp, vp, vp]
-    L.bp_get_episode_metrics.argtypes = [vp, vp, vp, vp]
-    if hasattr(L, "bp_get_episode_history"):
-        L.bp_get_episode_history.argtypes = [vp, vp, vp, vp, vp]
-    L.bp_start_uniform.argtypes = [C.c_uint64, C.c_int64, C.c_int64]
-    L.bp_start_uniform.restype = C.c_double
-    L.bp_debug_round2.argtypes = [vp, vp, C.c_int32, vp]
-    L.bp_copy_rows_masked.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int64, vp]
-    if hasattr(L, "bp_debug_scramble_hints"):
-        L.bp_debug_scramble_hints.argtypes = [vp, C.c_uint64, vp]
-    L.bp_costmap_update.argtypes = [vp, C.POINTER(BpCostmapConfig), vp, C.c_double, vp, vp]
-    for n in ("bp_nb_cap", "bp_obs_height", "bp_obs_width"):
-        getattr(L, n).argtypes = [vp]
-        getattr(L, n).restype = C.c_int32
-    L.bp_get_num_bodies.argtypes = [vp, vp]
-    L.bp_check_errors.argtypes = [vp, vp]
-    L.bp_kernel_time_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]
-    L.bp_enable_timing.argtypes = [vp, C.c_int32]
-    L.bp_get_step_cycles.argtypes = [vp, vp]
-    L.bp_set_step_cost_hint.argtypes = [vp, vp]
-    L.bp_sched_chunk.argtypes = [vp]
-    L.bp_sched_resident.argtypes = [vp]
-    L.bp_pair_mode.argtypes = [vp]
-    L.bp_get_pair_stats.argtypes = [vp, vp]
-    L.bp_bd_get_stragglers.argtypes = [vp, vp]
-    L.bp_sched_chunk.restype = C.c_int32
-    L.bp_sched_resident.restype = C.c_int32
-    if hasattr(L, "bp_device_shared"):    # ABI 11 (tools/ab_libs.sh loads older builds for same-box comparisons)
-        L.bp_device_shared.argtypes = [vp]
-        L.bp_device_shared.restype = C.c_int32
-        L.bp_bd_budget.argtypes = [vp]
-        L.bp_bd_budget.restype = C.c_int32
-        L.bp_launch_policy_query.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]
-        L.bp_get_cost_stats.argtypes = [vp, vp, C.c_int32, C.POINTER(C.c_int32)]
-    if hasattr(L, "bp_bd_get_cycle_skips"):
-        L.bp_bd_get_cycle_skips.argtypes = [vp, vp]
-    if hasattr(L, "bp_bd_step_async"):   # asynchronous step (absent from older builds loaded for same-box comparisons)
-        L.bp_bd_step_async.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.bp_bd_async_drain.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.bp_bd_async_open.argtypes = [vp]
-        L.bp_bd_async_open.restype = C.c_int32
-    if hasattr(L, "bp_bd_queue_open"):   # ready queue of the asynchronous step (absent from older builds loaded for same-box comparisons)
-        L.bp_bd_queue_open.argtypes = [vp, C.c_int32, vp]
-        L.bp_bd_queue_recv.argtypes = [vp, C.c_int32, C.c_int32] + [vp] * 16
-        L.bp_bd_queue_send.argtypes = [vp] * 7
-        L.bp_bd_queue_close.argtypes = [vp] * 9
-        L.bp_bd_queue_batch.argtypes = [vp]
-        L.bp_bd_queue_batch.restype = C.c_int32
-    if hasattr(L, "bp_task_metric_row"):   # episode metrics of box handles (absent from older builds loaded for same-box comparisons)
-        L.bp_bd_get_episode_boxes.argtypes = [vp, vp, vp]
-        L.bp_bd_get_completed.argtypes = [vp, vp]
-        L.bp_task_metric_row.argtypes = [C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, vp]
-    if hasattr(L, "bp_get_clock_stamps"):
-        L.bp_get_clock_stamps.argtypes = [vp, vp]
-    if hasattr(L, "bp_sched_warnings"):   # absent from libraries of ABI 6 (tools/ab_bench.sh loads older builds for same-box comparisons)
-        L.bp_sched_warnings.argtypes = [vp, vp]
-    L.bp_last_error.argtypes = [vp]
-    L.bp_last_error.restype = C.c_char_p
-    L.bp_debug_trace.argtypes = [vp, vp, C.c_int32]
-    L.bp_set_resettle.argtypes = [vp, C.c_int32]
-    L.bp_debug_prof.argtypes = [vp, vp]
-    L.bp_bd_sizeof_config.restype = C.c_int32
-    # (a build from before the episode metrics of these handles, loaded for a same-box comparison, has no robot_mass at the end and reads the rest)
-    if L.bp_bd_sizeof_config() not in (C.sizeof(BpBdConfig), C.sizeof(BpBdConfig) - (0 if hasattr(L, "bp_task_metric_row") else 8)):
-        raise BpError("bp_bd_config layout mismatch between _lib.BpBdConfig and the library")
-    L.bp_bd_create.argtypes = [C.POINTER(BpBdConfig), C.c_int32, C.c_int64, C.c_int32, C.POINTER(vp)]
-    L.bp_bd_load.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, vp, vp]
-    L.bp_bd_get_maps.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, vp]
-    L.bp_bd_get_state.argtypes = [vp, vp, vp, vp]
-    if hasattr(L, "bp_render"):
-        from .render import RenderArgs, RenderPrim
-        L.bp_sizeof_render_args.restype = C.c_int32
-        L.bp_sizeof_render_prim.restype = C.c_int32
-        if L.bp_sizeof_render_args() != C.sizeof(RenderArgs) or L.bp_sizeof_render_prim() != C.sizeof(RenderPrim):
-            raise BpError("bp_render_args / bp_render_prim layout mismatch between benchpush_amd.render and the library")
-        L.bp_set_render_table.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp]
-        L.bp_render.argtypes = [vp, C.POINTER(RenderArgs), vp, C.c_int32, vp, vp, vp, vp]
-    if hasattr(L, "bp_save_state"):   # state records (absent from older builds loaded for same-box comparisons)
-        L.bp_state_bytes.argtypes = [vp]
-        L.bp_state_bytes.restype = C.c_int64
-        L.bp_state_layout_id.argtypes = [vp]
-        L.bp_state_layout_id.restype = C.c_uint64
-        L.bp_save_state.argtypes = [vp, vp, C.c_int32, vp, vp]
-        L.bp_load_state.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, vp]
-        L.bp_clone_state.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, vp]
-        L.bp_state_layout_query.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_uint64)]
-    if hasattr(L, "bp_swath_cost"):   # swath costs (absent from older builds loaded for same-box comparisons)
-        L.bp_sizeof_swath_config.restype = C.c_int32
-        if L.bp_sizeof_swath_config() != C.sizeof(BpSwathConfig):
-            raise BpError("bp_swath_config layout mismatch between _lib.BpSwathConfig and the library")
-        L.bp_swath_cost.argtypes = [vp, C.POINTER(BpSwathConfig), vp, vp, vp, vp, vp, vp, vp, vp]
-    if hasattr(L, "bp_lattice_search"):   # lattice A* (absent from older builds loaded for same-box comparisons)
-        L.bp_sizeof_lattice_config.restype = C.c_int32
-        if L.bp_sizeof_lattice_config() != C.sizeof(BpLatticeConfig):
-            raise BpError("bp_lattice_config layout mismatch between _lib.BpLatticeConfig and the library")
-        L.bp_lattice_workspace_bytes.argtypes = [C.POINTER(BpLatticeConfig), C.c_int32]
-        L.bp_lattice_workspace_bytes.restype = C.c_int64
-        L.bp_lattice_search.argtypes = [vp, C.POINTER(BpLatticeConfig)] + [vp] * 10 + [C.c_int64] + [vp] * 7
-    if hasattr(L, "bp_track_path"):   # path tracking (absent from older builds loaded for same-box comparisons)
-        L.bp_sizeof_track_config.restype = C.c_int32
-        if L.bp_sizeof_track_config() != C.sizeof(BpTrackConfig):
-            raise BpError("bp_track_config layout mismatch between _lib.BpTrackConfig and the library")
-        L.bp_track_path.argtypes = [vp, C.POINTER(BpTrackConfig), vp, C.c_int64] + [vp] * 8
-    if hasattr(L, "bp_rrt_plan"):   # batched RRT and its waypoint controller (absent from older builds loaded for same-box comparisons)
-        L.bp_sizeof_rrt_config.restype = C.c_int32
-        L.bp_sizeof_track_wp_config.restype = C.c_int32
-        if L.bp_sizeof_rrt_config() != C.sizeof(BpRrtConfig) or L.bp_sizeof_track_wp_config() != C.sizeof(BpTrackWpConfig):
-            raise BpError("bp_rrt_config / bp_track_wp_config layout mismatch between _lib and the library")
-        L.bp_rrt_workspace_bytes.argtypes = [C.POINTER(BpRrtConfig), C.c_int32]
-        L.bp_rrt_workspace_bytes.restype = C.c_int64
-        L.bp_rrt_uniform.argtypes = [C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32]
-        L.bp_rrt_uniform.restype = C.c_double
-        L.bp_rrt_plan.argtypes = [vp, C.POINTER(BpRrtConfig), vp, vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_int64] + [vp] * 6
-        L.bp_track_waypoints.argtypes = [vp, C.POINTER(BpTrackWpConfig)] + [vp] * 7
-    if hasattr(L, "bp_gtsp_plan"):   # the GTSP push planner and its controller (absent from older builds loaded for same-box comparisons)
-        L.bp_sizeof_gtsp_config.restype = C.c_int32
-        if L.bp_sizeof_gtsp_config() != C.sizeof(BpGtspConfig):
-            raise BpError("bp_gtsp_config layout mismatch between _lib.BpGtspConfig and the library")
-        L.bp_gtsp_workspace_bytes.argtypes = [C.POINTER(BpGtspConfig), C.c_int32]
-        L.bp_gtsp_workspace_bytes.restype = C.c_int64
-        L.bp_gtsp_plan.argtypes = [vp, C.POINTER(BpGtspConfig), vp, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_int64] + [vp] * 10
-        L.bp_gtsp_track.argtypes = [vp, C.POINTER(BpGtspConfig)] + [vp] * 9
-    if hasattr(L, "bp_replay_observe"):   # replay buffer on the ready queue (absent from older builds loaded for same-box comparisons)
-        L.bp_sizeof_replay_desc.restype = C.c_int32
-        L.bp_sizeof_replay_batch.restype = C.c_int32
-        if L.bp_sizeof_replay_desc() != C.sizeof(BpReplayDesc) or L.bp_sizeof_replay_batch() != C.sizeof(BpReplayBatch):
-            raise BpError("bp_replay_desc / bp_replay_batch layout mismatch between _lib and the library")
-        L.bp_replay_index.argtypes = [C.c_uint64, C.c_int64, C.c_int32, C.c_int64]
-        L.bp_replay_index.restype = C.c_int64
-        L.bp_replay_observe.argtypes = [C.POINTER(BpReplayDesc)] + [vp] * 7 + [C.c_int32, C.c_int32, vp]
-        L.bp_replay_record.argtypes = [C.POINTER(BpReplayDesc), vp, vp, vp, C.c_int32, vp]
-        L.bp_replay_sample.argtypes = [C.POINTER(BpReplayDesc), C.c_int32, C.c_uint64, C.POINTER(BpReplayBatch), vp]
+    for name, (restype, argtypes, group) in list(ABI.items()) + list(DIAGNOSTIC_ABI.items()):
+        if group is None or hasattr(L, group):   # (a symbol that is missing although its group is there: AttributeError)
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
+    for sizeof, struct, what in LAYOUTS:
+        if hasattr(L, sizeof):
+            sizes = {C.sizeof(struct)}
+            if struct is BpBdConfig and not hasattr(L, "bp_task_metric_row"):
+                sizes.add(C.sizeof(struct) - 8)   # a build from before the episode metrics of these handles has no robot_mass at the end and reads the rest
+            if getattr(L, sizeof)() not in sizes:
+                raise BpError(what)
     _lib = L
     return L
 

@@ -15,7 +15,8 @@ import torch
 from .. import _lib
 from ..area_clearing_scenario import area_clearing_params, area_clearing_physics_params, env_layout, generate_trials, goal_points
 from ..config import default_cfg, merge_user_cfg
-from ..gym_shim import Env, spaces
+from ..gym_shim import spaces
+from .batched import _AdapterBase
 from .box_delivery import BatchedBoxDeliveryEnv, low_dim_observation
 from .ship_ice import _ptr
 
@@ -64,13 +65,6 @@ class BatchedAreaClearingEnv(BatchedBoxDeliveryEnv):
         return super().step_async(actions, budget)
 
     # -- the planning baseline's device calls (DESIGN.md "GTSP") --------------------------------------------
-    def _need(self, fn, t, name, dtypes, shape):
-        dtypes = dtypes if isinstance(dtypes, tuple) else (dtypes,)
-        if not isinstance(t, torch.Tensor) or t.dtype not in dtypes or t.device != self.device or not t.is_contiguous():
-            raise ValueError("%s: %s must be a contiguous %s tensor on %s" % (fn, name, " / ".join(map(str, dtypes)), self.device))
-        if t.dim() != len(shape) or any(a is not None and a != b for a, b in zip(shape, t.shape)):
-            raise ValueError("%s: %s has shape %s, expected %s" % (fn, name, tuple(t.shape), list(shape)))
-
     def push_box_polys(self):
         """The box rows of ``world_polys()``: (verts [E, nbox, 20, 2] f64, counts [E, nbox] i32), contiguous."""
         verts, cnt = self.world_polys()
@@ -118,7 +112,7 @@ class BatchedAreaClearingEnv(BatchedBoxDeliveryEnv):
         Returns ``planning.GTSPPlan``.  Raises ValueError, before any launch, for a wrong dtype, device, shape or a non-contiguous tensor; BpError for
         what the library refuses.  Touches no environment state."""
         from ..planning import GTSPPlan
-        E, dev, fn = self.num_envs, self.device, "gtsp_plan"
+        E, dev, need = self.num_envs, self.device, self._need("gtsp_plan")
         if poses is None:
             poses = self.info[:, :3].contiguous()
         if (boxes is None) != (counts is None):
@@ -127,30 +121,30 @@ class BatchedAreaClearingEnv(BatchedBoxDeliveryEnv):
             boxes, counts = self.push_box_polys()
         if goals is None:
             goals = self.boundary_goals()[1]
-        self._need(fn, goals, "goals", torch.float64, (None, 4))
+        need(goals, "goals", torch.float64, (None, 4))
         cfg = self._gtsp_struct(config, goals)
         if goals.shape[0] != cfg.num_goals:
             raise ValueError("gtsp_plan: goals has %d rows, config.num_goals is %d" % (goals.shape[0], cfg.num_goals))
-        self._need(fn, poses, "poses", torch.float64, (E, 3))
-        self._need(fn, boxes, "boxes", torch.float64, (E, None, None, 2))
-        self._need(fn, counts, "counts", torch.int32, (E, boxes.shape[1]))
+        need(poses, "poses", torch.float64, (E, 3))
+        need(boxes, "boxes", torch.float64, (E, None, None, 2))
+        need(counts, "counts", torch.int32, (E, boxes.shape[1]))
         if active is not None:
-            self._need(fn, active, "active", (torch.bool, torch.uint8), (E,))
+            need(active, "active", (torch.bool, torch.uint8), (E,))
         nm, G = max(int(cfg.max_boxes), 0), int(cfg.num_goals)
         Nm = nm * G + 1
         if out is not None:
-            self._need(fn, out.status, "out.status", torch.int32, (E,))
-            self._need(fn, out.n_push, "out.n_push", torch.int32, (E,))
-            self._need(fn, out.tour, "out.tour", torch.int32, (E, nm))
-            self._need(fn, out.cost, "out.cost", torch.int32, (E,))
-            self._need(fn, out.paths, "out.paths", torch.float64, (E, 2 * nm + 1, 3))
-            self._need(fn, out.lengths, "out.lengths", torch.int32, (E,))
-            self._need(fn, out.track_id, "out.track_id", torch.int32, (E,))
-            self._need(fn, out.track_setpoint, "out.track_setpoint", torch.float64, (E, 2))
+            need(out.status, "out.status", torch.int32, (E,))
+            need(out.n_push, "out.n_push", torch.int32, (E,))
+            need(out.tour, "out.tour", torch.int32, (E, nm))
+            need(out.cost, "out.cost", torch.int32, (E,))
+            need(out.paths, "out.paths", torch.float64, (E, 2 * nm + 1, 3))
+            need(out.lengths, "out.lengths", torch.int32, (E,))
+            need(out.track_id, "out.track_id", torch.int32, (E,))
+            need(out.track_setpoint, "out.track_setpoint", torch.float64, (E, 2))
             if return_weights:
                 if out.weights is None:
                     raise ValueError("gtsp_plan: return_weights needs out.weights")
-                self._need(fn, out.weights, "out.weights", torch.int32, (E, Nm, Nm))
+                need(out.weights, "out.weights", torch.int32, (E, Nm, Nm))
         else:
             z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)   # noqa: E731
             big = nm > _lib.GTSP_MAX_BOXES or G > _lib.GTSP_MAX_GOALS        # a config that the library is about to refuse: allocate nothing large
@@ -158,13 +152,13 @@ class BatchedAreaClearingEnv(BatchedBoxDeliveryEnv):
                            z(E, torch.int32), z(E, torch.int32), z((E, 2), torch.float64),
                            z((E, Nm, Nm), torch.int32) if return_weights and not big else None)
         if workspace is None:
-            need = self.L.bp_gtsp_workspace_bytes(C.byref(cfg), E)
+            nbytes = self.L.bp_gtsp_workspace_bytes(C.byref(cfg), E)
             workspace = getattr(self, "_gtsp_ws", None)
-            if need > 0 and (workspace is None or workspace.numel() < need):
-                workspace = self._gtsp_ws = torch.empty(int(need), dtype=torch.uint8, device=dev)
+            if nbytes > 0 and (workspace is None or workspace.numel() < nbytes):
+                workspace = self._gtsp_ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
             elif workspace is None:
                 workspace = torch.empty(16, dtype=torch.uint8, device=dev)     # a config that the library is about to refuse
-        self._need(fn, workspace, "workspace", torch.uint8, (None,))
+        need(workspace, "workspace", torch.uint8, (None,))
         _lib.check(self.L, self.h, self.L.bp_gtsp_plan(
             self.h, C.byref(cfg), _ptr(poses), _ptr(boxes) if boxes.numel() else None, _ptr(counts) if boxes.numel() else None,
             int(boxes.shape[1]) if boxes.numel() else 0, int(boxes.shape[2]), _ptr(goals), _ptr(active), _ptr(workspace), int(workspace.numel()),
@@ -179,22 +173,22 @@ class BatchedAreaClearingEnv(BatchedBoxDeliveryEnv):
         reference's values); out None or (actions, diag) to be overwritten.  Returns (actions float64 [E, 2] -- what ``step`` takes with
         action_type 'velocity' --, diag int32 [E] = current_point_id).  An env that is not active, has a length below 2, or a non-finite pose or
         counted waypoint gets NaN and -1, and its state is left as it is."""
-        E, dev, fn = self.num_envs, self.device, "track_pushes"
+        E, dev, need = self.num_envs, self.device, self._need("track_pushes")
         cfg = self._gtsp_struct(config)
         P = 2 * int(cfg.max_boxes) + 1
-        self._need(fn, plan.paths, "plan.paths", torch.float64, (E, P, 3))
-        self._need(fn, plan.lengths, "plan.lengths", torch.int32, (E,))
-        self._need(fn, tracker.ids, "tracker.ids", torch.int32, (E,))
-        self._need(fn, tracker.setpoint, "tracker.setpoint", torch.float64, (E, 2))
+        need(plan.paths, "plan.paths", torch.float64, (E, P, 3))
+        need(plan.lengths, "plan.lengths", torch.int32, (E,))
+        need(tracker.ids, "tracker.ids", torch.int32, (E,))
+        need(tracker.setpoint, "tracker.setpoint", torch.float64, (E, 2))
         if poses is None:
             poses = self.info[:, :3].contiguous()
-        self._need(fn, poses, "poses", torch.float64, (E, 3))
+        need(poses, "poses", torch.float64, (E, 3))
         if active is not None:
-            self._need(fn, active, "active", (torch.bool, torch.uint8), (E,))
+            need(active, "active", (torch.bool, torch.uint8), (E,))
         if out is not None:
             actions, diag = out
-            self._need(fn, actions, "out[0]", torch.float64, (E, 2))
-            self._need(fn, diag, "out[1]", torch.int32, (E,))
+            need(actions, "out[0]", torch.float64, (E, 2))
+            need(diag, "out[1]", torch.int32, (E,))
         else:
             actions, diag = torch.zeros((E, 2), dtype=torch.float64, device=dev), torch.zeros(E, dtype=torch.int32, device=dev)
         _lib.check(self.L, self.h, self.L.bp_gtsp_track(self.h, C.byref(cfg), _ptr(plan.paths), _ptr(plan.lengths), _ptr(poses), _ptr(active),
@@ -203,7 +197,7 @@ class BatchedAreaClearingEnv(BatchedBoxDeliveryEnv):
         return actions, diag
 
 
-class AreaClearingEnv(Env):
+class AreaClearingEnv(_AdapterBase):
     """Reference-shaped single environment (E = 1): reset()/step() returns and info keys of area_clearing.py:563-778."""
 
     metadata = {"render_modes": ["human", "rgb_array"], "render_fps": 4}
@@ -268,15 +262,11 @@ class AreaClearingEnv(Env):
         return self._b.obs[0].cpu().numpy()
 
     def reset(self, seed=None, options=None):
-        self.episode_idx = 0 if self.episode_idx is None else self.episode_idx + 1
-        if self.episode_idx:
-            self._b.check_errors()   # capacity flags of the episode that just ended (raises BpError)
-        self._b.reset()
-        self.t = 0
+        self._begin_episode()
         it = self._b.info[0].cpu().numpy()
         boxes = self._boxes()
         self.box_clearance_statuses = [False] * self.num_box
-        info = {"state": (round(float(it[0]), 2), round(float(it[1]), 2), round(float(it[2]), 2)), "total_work": 0, "obs": boxes, "box_count": 0,
+        info = {"state": self._state3(it), "total_work": 0, "obs": boxes, "box_count": 0,
                 "boundary": self.boundary_vertices, "walls": self.walls, "static_obstacles": self.static_obstacles,
                 "goal_positions": self.goal_points, "low_level_observation": self._low_dim(boxes)}
         return self._result(info), info
@@ -288,7 +278,7 @@ class AreaClearingEnv(Env):
         it = self._b.info[0].cpu().numpy()
         boxes = self._boxes()
         self.box_clearance_statuses = self._statuses(boxes)
-        info = {"state": (round(float(it[0]), 2), round(float(it[1]), 2), round(float(it[2]), 2)), "total_work": float(it[3]),
+        info = {"state": self._state3(it), "total_work": float(it[3]),
                 "collision reward": float(it[4]), "diff_reward": float(it[5]), "box_completed_reward": float(it[6]), "obs": boxes,
                 "box_completed_statuses": self.box_clearance_statuses, "box_count": int(it[7]), "ministeps": float(it[8]),
                 "low_level_observation": self._low_dim(boxes)}
@@ -296,16 +286,6 @@ class AreaClearingEnv(Env):
                 bool(self._b.truncated[0].item()), info)
 
     _STATE_FIELDS = ("t", "episode_idx", "box_clearance_statuses")
-
-    def save_state(self):
-        """The whole env between two steps as an ``EnvState`` (benchpush_amd/state.py): the device state record plus this adapter's own fields."""
-        from ..state import adapter_save
-        return adapter_save(self, self._STATE_FIELDS)
-
-    def restore_state(self, state):
-        """Back to a state of save_state(): the following steps repeat bit for bit what followed the save."""
-        from ..state import adapter_restore
-        adapter_restore(self, state, self._STATE_FIELDS)
 
     def render(self, mode="human", close=False):
         """rgb_array: the frame of this env with the controller's current waypoints as the path (numpy [H, W, 3]; benchpush_amd/render.py).
@@ -320,6 +300,3 @@ class AreaClearingEnv(Env):
             snap = snapshot_path(self.cfg, self.episode_idx, self.t)
         _, wp, nwp = self._b.box_state()
         return adapter_render(self, mode, wp[0, : int(nwp[0]), :2], snap)
-
-    def close(self):
-        self._b.close()

@@ -17,8 +17,9 @@ import torch
 from .. import _lib
 from ..box_delivery_scenario import box_delivery_params, box_delivery_physics_params, generate_trials
 from ..config import default_cfg, merge_user_cfg
-from ..gym_shim import Env, spaces
+from ..gym_shim import spaces
 from ..scenario import poly_centroid
+from .batched import _AdapterBase
 from .ship_ice import BatchedShipIceEnv, _ptr
 
 __all__ = ["BatchedBoxDeliveryEnv", "BoxDeliveryEnv", "AsyncQueue", "BD_INFO_KEYS"]
@@ -54,12 +55,8 @@ class BatchedBoxDeliveryEnv(BatchedShipIceEnv):
         return _lib.make_bd_config(self.params, self.bd_params, self.cfg)
 
     def __init__(self, num_envs, cfg=None, trials=None, device="cuda:0", env_id_offset=0, num_trials=32, seed=None, bd_overrides=None):
-        if not torch.cuda.is_available():
-            raise _lib.BpError("%s needs a ROCm GPU (torch.cuda.is_available() is False); no CPU fallback" % type(self).__name__)
-        self.L = _lib.load()
+        self._open(num_envs, device, env_id_offset)
         self.cfg = self._task_cfg(cfg)
-        self.num_envs = int(num_envs)
-        self.device = torch.device(device)
         self.params = self._physics_params(self.cfg)
         self.bd_params = self._task_params(self.cfg)
         if bd_overrides:   # constants of the reference that are not in its config (e.g. STEP_LIMIT, box_delivery_env.py:62): tests shorten them
@@ -72,10 +69,7 @@ class BatchedBoxDeliveryEnv(BatchedShipIceEnv):
         if self._same_box_count and any(len(t["boxes"]) != nbox for t in trials):
             raise ValueError("all trials must hold the same number of boxes")
         self.bd_params["num_boxes"] = nbox
-        bcfg = self._bd_config()
-        self.h = C.c_void_p()
-        dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        _lib.check(self.L, None, self.L.bp_bd_create(C.byref(bcfg), self.num_envs, int(env_id_offset), dev_index, C.byref(self.h)), "bp_bd_create")
+        self._create(self.L.bp_bd_create, self._bd_config())
         c = lambda a, dt: np.ascontiguousarray(a, dt)
         starts = c(np.stack([t["start"] for t in trials]), np.float64)
         boxes = c(np.stack([t["boxes"] for t in trials]), np.float64)
@@ -90,12 +84,9 @@ class BatchedBoxDeliveryEnv(BatchedShipIceEnv):
         st = c(np.stack([pad(t["statics"][4], 3) for t in trials]), np.int32)
         p = lambda a: a.ctypes.data_as(C.c_void_p)
         _lib.check(self.L, self.h, self.L.bp_bd_load(self.h, len(trials), nbox, p(starts), p(boxes), ns, p(sv), p(sc), p(sp), p(sr), p(st)), "bp_bd_load")
-        self._alloc_io()
         lp = self.L.bp_obs_height(self.h)
-        self.obs_shape = (lp, lp, 4)
-        self.obs = torch.zeros((self.num_envs,) + self.obs_shape, dtype=torch.uint8, device=self.device)
         self.action_dim = 2 if self.cfg.agent.action_type == "velocity" else 1
-        self._actions = torch.zeros(self.num_envs * self.action_dim, dtype=torch.float64, device=self.device)
+        self._alloc_io((lp, lp, 4), self.action_dim)
 
     def step(self, actions):
         """actions: [E] heading in [-1, 1] / position index, or [E, 2] = (linear, angular) speed for 'velocity'."""
@@ -305,7 +296,7 @@ def low_dim_observation(polys):
     return out
 
 
-class BoxDeliveryEnv(Env):
+class BoxDeliveryEnv(_AdapterBase):
     """Reference-shaped single environment (E = 1): reset()/step() returns and info keys of box_delivery_env.py:578-830."""
 
     metadata = {"render_modes": ["human", "rgb_array"], "render_fps": 4}
@@ -345,17 +336,13 @@ class BoxDeliveryEnv(Env):
 
     def _info(self, it, boxes, alive):
         self.box_clearance_statuses = [not bool(a) for a in alive]
-        return {"state": (round(float(it[0]), 2), round(float(it[1]), 2), round(float(it[2]), 2)), "cumulative_distance": float(it[3]),
+        return {"state": self._state3(it), "cumulative_distance": float(it[3]),
                 "cumulative_boxes": int(it[4]), "cumulative_reward": float(it[5]), "total_work": float(it[6]), "obs": boxes,
                 "box_completed_statuses": self.box_clearance_statuses, "goal_positions": self.goal_points, "ministeps": float(it[7]),
                 "inactivity": int(it[8])}
 
     def reset(self, seed=None, options=None):
-        self.episode_idx = 0 if self.episode_idx is None else self.episode_idx + 1
-        if self.episode_idx:
-            self._b.check_errors()   # capacity flags of the episode that just ended (raises BpError)
-        self._b.reset()
-        self.t = 0
+        self._begin_episode()
         boxes, alive = self._boxes()
         # low_dim_state: reset() returns <|centroid| of every box> (box_delivery_env.py:606-607,1025-1037); step() always returns the
         # image observation (box_delivery_env.py:807)
@@ -373,22 +360,9 @@ class BoxDeliveryEnv(Env):
 
     _STATE_FIELDS = ("t", "episode_idx", "box_clearance_statuses")
 
-    def save_state(self):
-        """The whole env between two steps as an ``EnvState`` (benchpush_amd/state.py): the device state record plus this adapter's own fields."""
-        from ..state import adapter_save
-        return adapter_save(self, self._STATE_FIELDS)
-
-    def restore_state(self, state):
-        """Back to a state of save_state(): the following steps repeat bit for bit what followed the save."""
-        from ..state import adapter_restore
-        adapter_restore(self, state, self._STATE_FIELDS)
-
     def render(self, mode="human", close=False):
         """rgb_array: the frame of this env with the controller's current waypoints as the path (numpy [H, W, 3]; benchpush_amd/render.py).
         human: no window and no snapshot (the reference's save branch is disabled, box_delivery_env.py:1275): warns once, returns None."""
         from ..render import adapter_render
         _, wp, nwp = self._b.box_state()
         return adapter_render(self, mode, wp[0, : int(nwp[0]), :2], None)
-
-    def close(self):
-        self._b.close()

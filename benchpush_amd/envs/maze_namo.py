@@ -16,9 +16,10 @@ import torch
 
 from .. import _lib
 from ..config import default_cfg, maze_physics_params, maze_walls, merge_user_cfg
-from ..gym_shim import Env, spaces
+from ..gym_shim import spaces
 from ..maze_scenario import generate_layout
 from ..scenario import poly_centroid
+from .batched import _AdapterBase
 from .ship_ice import BatchedShipIceEnv, _ptr
 
 __all__ = ["BatchedMazeEnv", "MazeNAMO", "default_layouts"]
@@ -50,15 +51,9 @@ class BatchedMazeEnv(BatchedShipIceEnv):
 
     render_task = "maze"
 
-
     def __init__(self, num_envs, cfg=None, layouts=None, device="cuda:0", env_id_offset=0, num_layouts=64, base_seed=0):
-        if not torch.cuda.is_available():
-            raise _lib.BpError("BatchedMazeEnv needs a ROCm GPU (torch.cuda.is_available() is False); no CPU fallback")
-        self.L = _lib.load()
+        self._open(num_envs, device, env_id_offset)
         self.cfg = _maze_cfg(cfg)
-        self.num_envs = int(num_envs)
-        self.env_id_offset = int(env_id_offset)
-        self.device = torch.device(device)
         self.params = maze_physics_params(self.cfg)
         self.goal = (self.cfg.env.goal_x, self.cfg.env.goal_y)
         self.max_yaw_rate_step = (math.pi / 2) / 15
@@ -72,9 +67,7 @@ class BatchedMazeEnv(BatchedShipIceEnv):
         tail = ((rv[1][0] + rv[2][0]) / 2, (rv[1][1] + rv[2][1]) / 2)
         bcfg = _lib.make_config(self.params, rv, head, tail, env_kind=_lib.ENV_MAZE, wheel_vertices=self.cfg.robot.wheel_vertices,
                                 obstacle_size=self.cfg.obstacle_size)
-        self.h = C.c_void_p()
-        dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        _lib.check(self.L, None, self.L.bp_create(C.byref(bcfg), self.num_envs, int(env_id_offset), dev_index, C.byref(self.h)), "bp_create")
+        self._create(self.L.bp_create, bcfg)
         nbox = len(layouts[0]["centres"])
         if any(len(l["centres"]) != nbox for l in layouts):
             raise ValueError("all layouts must hold the same number of boxes")
@@ -96,13 +89,6 @@ class BatchedMazeEnv(BatchedShipIceEnv):
         return out
 
     # -- the planning baseline's device calls (DESIGN.md "RRT") ---------------------------------------------
-    def _need(self, fn, t, name, dtypes, shape):
-        dtypes = dtypes if isinstance(dtypes, tuple) else (dtypes,)
-        if not isinstance(t, torch.Tensor) or t.dtype not in dtypes or t.device != self.device or not t.is_contiguous():
-            raise ValueError("%s: %s must be a contiguous %s tensor on %s" % (fn, name, " / ".join(map(str, dtypes)), self.device))
-        if t.dim() != len(shape) or any(a is not None and a != b for a, b in zip(shape, t.shape)):
-            raise ValueError("%s: %s has shape %s, expected %s" % (fn, name, tuple(t.shape), list(shape)))
-
     def box_polys(self):
         """The box rows of ``world_polys()``: (verts [E, nbox, 20, 2] f64, counts [E, nbox] i32), contiguous."""
         verts, cnt = self.world_polys()
@@ -139,7 +125,7 @@ class BatchedMazeEnv(BatchedShipIceEnv):
         [E, max_waypoints, 2], lengths int32 [E].  Raises ValueError, before any launch, for a wrong dtype, device, shape or a non-contiguous tensor;
         BpError for what the library refuses.  Touches no environment state."""
         from ..planning import RRTConfig, RRTPlan
-        E, dev, fn = self.num_envs, self.device, "rrt_plan"
+        E, dev, need = self.num_envs, self.device, self._need("rrt_plan")
         config = config or RRTConfig()
         cfg = config.as_struct(self)
         if starts is None:
@@ -158,33 +144,33 @@ class BatchedMazeEnv(BatchedShipIceEnv):
             boxes, counts = self.box_polys()
         if streams is None:
             streams = self.env_id_offset + torch.arange(E, dtype=torch.int64, device=dev)
-        self._need(fn, starts, "starts", torch.float64, (E, 2))
-        self._need(fn, goals, "goals", torch.float64, (E, 2))
-        self._need(fn, walls, "walls", torch.float64, (None, 4))
-        self._need(fn, boxes, "boxes", torch.float64, (E, None, None, 2))
-        self._need(fn, counts, "counts", torch.int32, (E, boxes.shape[1]))
-        self._need(fn, streams, "streams", torch.int64, (E,))
+        need(starts, "starts", torch.float64, (E, 2))
+        need(goals, "goals", torch.float64, (E, 2))
+        need(walls, "walls", torch.float64, (None, 4))
+        need(boxes, "boxes", torch.float64, (E, None, None, 2))
+        need(counts, "counts", torch.int32, (E, boxes.shape[1]))
+        need(streams, "streams", torch.int64, (E,))
         if active is not None:
-            self._need(fn, active, "active", (torch.bool, torch.uint8), (E,))
+            need(active, "active", (torch.bool, torch.uint8), (E,))
         P = int(cfg.max_waypoints)
         if out is not None:
-            self._need(fn, out.status, "out.status", torch.int32, (E,))
-            self._need(fn, out.n_nodes, "out.n_nodes", torch.int32, (E, 2))
-            self._need(fn, out.iterations, "out.iterations", torch.int32, (E, 2))
-            self._need(fn, out.paths, "out.paths", torch.float64, (E, P, 2))
-            self._need(fn, out.lengths, "out.lengths", torch.int32, (E,))
+            need(out.status, "out.status", torch.int32, (E,))
+            need(out.n_nodes, "out.n_nodes", torch.int32, (E, 2))
+            need(out.iterations, "out.iterations", torch.int32, (E, 2))
+            need(out.paths, "out.paths", torch.float64, (E, P, 2))
+            need(out.lengths, "out.lengths", torch.int32, (E,))
         else:
             out = RRTPlan(torch.zeros(E, dtype=torch.int32, device=dev), torch.zeros((E, 2), dtype=torch.int32, device=dev),
                           torch.zeros((E, 2), dtype=torch.int32, device=dev), torch.zeros((E, max(P, 0), 2), dtype=torch.float64, device=dev),
                           torch.zeros(E, dtype=torch.int32, device=dev))
         if workspace is None:
-            need = self.L.bp_rrt_workspace_bytes(C.byref(cfg), E)
+            nbytes = self.L.bp_rrt_workspace_bytes(C.byref(cfg), E)
             workspace = getattr(self, "_rrt_ws", None)
-            if need > 0 and (workspace is None or workspace.numel() < need):
-                workspace = self._rrt_ws = torch.empty(int(need), dtype=torch.uint8, device=dev)
+            if nbytes > 0 and (workspace is None or workspace.numel() < nbytes):
+                workspace = self._rrt_ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
             elif workspace is None:
                 workspace = torch.empty(16, dtype=torch.uint8, device=dev)     # a config that the library is about to refuse
-        self._need(fn, workspace, "workspace", torch.uint8, (None,))
+        need(workspace, "workspace", torch.uint8, (None,))
         _lib.check(self.L, self.h, self.L.bp_rrt_plan(
             self.h, C.byref(cfg), _ptr(starts), _ptr(goals), _ptr(walls) if walls.shape[0] else None, int(walls.shape[0]),
             _ptr(boxes) if boxes.numel() else None, _ptr(counts) if boxes.numel() else None, int(boxes.shape[1]) if boxes.numel() else 0,
@@ -198,19 +184,19 @@ class BatchedMazeEnv(BatchedShipIceEnv):
         or None (info[:, :3]); active bool / uint8 [E] or None; Lfc and dt as in rrt_config.yaml; action_scale None: max_yaw_rate_step; out None or
         (actions, diag) to be overwritten.  Returns (actions float64 [E] -- what ``step`` takes --, diag int32 [E, 2] = nearest and target index).  An
         env that is not active, has a length below 1, or a non-finite pose or counted waypoint gets NaN and (-1, -1)."""
-        E, dev, fn = self.num_envs, self.device, "track_waypoints"
-        self._need(fn, paths, "paths", torch.float64, (E, None, 2))
+        E, dev, need = self.num_envs, self.device, self._need("track_waypoints")
+        need(paths, "paths", torch.float64, (E, None, 2))
         if lengths is not None:
-            self._need(fn, lengths, "lengths", torch.int32, (E,))
+            need(lengths, "lengths", torch.int32, (E,))
         if poses is None:
             poses = self.info[:, :3].contiguous()
-        self._need(fn, poses, "poses", torch.float64, (E, 3))
+        need(poses, "poses", torch.float64, (E, 3))
         if active is not None:
-            self._need(fn, active, "active", (torch.bool, torch.uint8), (E,))
+            need(active, "active", (torch.bool, torch.uint8), (E,))
         if out is not None:
             actions, diag = out
-            self._need(fn, actions, "out[0]", torch.float64, (E,))
-            self._need(fn, diag, "out[1]", torch.int32, (E, 2))
+            need(actions, "out[0]", torch.float64, (E,))
+            need(diag, "out[1]", torch.int32, (E, 2))
         else:
             actions, diag = torch.zeros(E, dtype=torch.float64, device=dev), torch.zeros((E, 2), dtype=torch.int32, device=dev)
         cfg = _lib.BpTrackWpConfig(P=int(paths.shape[1]), pad_=0, Lfc=float(Lfc), dt=float(dt),
@@ -220,7 +206,7 @@ class BatchedMazeEnv(BatchedShipIceEnv):
         return actions, diag
 
 
-class MazeNAMO(Env):
+class MazeNAMO(_AdapterBase):
     """Reference-shaped single environment (E = 1): reset()/step() returns and info keys of maze_NAMO_env.py:325-485."""
 
     metadata = {"render_modes": ["human", "rgb_array"], "render_fps": 4}
@@ -273,18 +259,13 @@ class MazeNAMO(Env):
         return self._low_dim(obstacles, it) if self.low_dim_state else self._b.obs[0].cpu().numpy()
 
     def reset(self, seed=None, options=None):
-        self.episode_idx = 0 if self.episode_idx is None else self.episode_idx + 1
-        if self.episode_idx:
-            self._b.check_errors()   # capacity flags of the episode that just ended (raises BpError)
-        self._b.reset()
-        self.t = 0
+        self._begin_episode()
         self.total_work = [0, []]
         self.wall_collision = False
         it = self._b.info[0].cpu().numpy()
         obstacles = self._polys()
         self.obstacles = obstacles
-        info = {"state": (round(float(it[0]), 2), round(float(it[1]), 2), round(float(it[2]), 2)), "total_work": self.total_work[0],
-                "obs": obstacles, "box_count": 0, "goal_dt": self._goal_dt, "m_to_pix_scale": self.cfg.occ.m_to_pix_scale}
+        info = {"state": self._state3(it), "total_work": self.total_work[0], "obs": obstacles, "box_count": 0, "goal_dt": self._goal_dt, "m_to_pix_scale": self.cfg.occ.m_to_pix_scale}
         return self._observation(obstacles, it), info
 
     def step(self, action):
@@ -299,7 +280,7 @@ class MazeNAMO(Env):
         self.total_work[0] = float(it[3])
         self.total_work[1].append(float(it[4]))
         self.wall_collision = bool(it[10])
-        info = {"state": (round(float(it[0]), 2), round(float(it[1]), 2), round(float(it[2]), 2)), "total_work": self.total_work[0],
+        info = {"state": self._state3(it), "total_work": self.total_work[0],
                 "collision reward": float(it[5]), "scaled collision reward": float(it[6]), "dist increment reward": float(it[7]),
                 "trial_success": bool(it[8]), "obs": obstacles}
         if self.cfg.log_obs:
@@ -319,16 +300,6 @@ class MazeNAMO(Env):
 
     _STATE_FIELDS = ("t", "total_work", "episode_idx", "path", "obstacles", "wall_collision")
 
-    def save_state(self):
-        """The whole env between two steps as an ``EnvState`` (benchpush_amd/state.py): the device state record plus this adapter's own fields."""
-        from ..state import adapter_save
-        return adapter_save(self, self._STATE_FIELDS)
-
-    def restore_state(self, state):
-        """Back to a state of save_state(): the following steps repeat bit for bit what followed the save."""
-        from ..state import adapter_restore
-        adapter_restore(self, state, self._STATE_FIELDS)
-
     def update_path(self, new_path, scatter=False):
         self.path = new_path
 
@@ -338,6 +309,3 @@ class MazeNAMO(Env):
         from ..render import adapter_render, snapshot_path
         snap = snapshot_path(self.cfg, self.episode_idx, self.t) if mode == "human" and self.cfg.get("render_snapshot", False) else None
         return adapter_render(self, mode, self.path, snap)
-
-    def close(self):
-        self._b.close()

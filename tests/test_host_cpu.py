@@ -364,6 +364,42 @@ def test_bench_output_dump_is_float_bounded_and_seeded(tmp_path, monkeypatch):
     assert (bench.DUMP_OBS_BYTES // per_env_f32) * per_env_f32 + 4096 * (8 + 4 + 4 + 8 * 32 + 8) <= 64 << 20
 
 
+def _header_prototypes():
+    """{name: (return type without blanks, parameter count)} of every bp_* prototype of include/benchpush_amd.h (a prototype runs up to its `;`)."""
+    code = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(os.path.join(ROOT, "include", "benchpush_amd.h")).read(), flags=re.S)
+    code = "\n".join(l for l in code.splitlines() if not l.lstrip().startswith("#") and 'extern "C"' not in l)
+    protos = {}
+    for chunk in code.split(";"):
+        m = re.match(r"^(?P<ret>[\w\s\*]+?)\s*\b(?P<name>bp_[a-z_0-9]+)\s*\((?P<args>[^()]*)\)$", chunk.strip(), flags=re.S)
+        if m:
+            args = m.group("args").strip()
+            assert m.group("name") not in protos, m.group("name")
+            protos[m.group("name")] = (re.sub(r"\s+", "", m.group("ret")), 0 if args in ("", "void") else args.count(",") + 1)
+    return protos
+
+
+def test_ctypes_declarations_match_the_header_prototypes():
+    """_lib.ABI against include/benchpush_amd.h: every symbol of the table is declared, with as many parameters as the table has argtypes and a return
+    type of the table's width (a missing 64-bit restype truncates a pointer-sized value silently); and every prototype is in the table."""
+    from benchpush_amd import _lib
+    protos = _header_prototypes()
+    assert len(protos) > 90 and protos["bp_create"] == ("int", 5) and protos["bp_abi_version"] == ("int32_t", 0)
+    assert protos["bp_last_error"] == ("constchar*", 1) and protos["bp_state_layout_id"] == ("uint64_t", 1)
+    restypes = {"int": (C.c_int, C.c_int32), "int32_t": (C.c_int, C.c_int32), "int64_t": (C.c_int64,), "uint64_t": (C.c_uint64,),
+                "double": (C.c_double,), "constchar*": (C.c_char_p,)}
+    for name, (restype, argtypes, group) in _lib.ABI.items():
+        assert name in protos, name
+        ret, nparams = protos[name]
+        assert len(argtypes) == nparams, (name, len(argtypes), nparams)
+        assert restype in restypes[ret], (name, restype, ret)
+        assert group is None or group in _lib.ABI, (name, group)
+    c_only = {}   # prototypes that the Python binding has no use for: name -> reason (none today)
+    assert set(protos) - set(_lib.ABI) == set(c_only)
+    assert not set(_lib.DIAGNOSTIC_ABI) & set(protos)      # the twins' hooks are the library's only entry points outside the header
+    assert sorted(_lib.EXPORTS) == sorted(_lib.ABI) and len(set(_lib.EXPORTS)) == len(_lib.EXPORTS)
+    assert {fn for fn, _, _ in _lib.LAYOUTS} == {n for n in _lib.ABI if "sizeof" in n}
+
+
 def test_bench_has_the_full_and_dump_options():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
     assert p.returncode == 0 and "--full" in p.stdout.decode() and "--dump-outputs" in p.stdout.decode()
