@@ -55,6 +55,15 @@ class BpReplayBatch(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("state", "next_state", "action", "reward", "ministeps", "nonfinal", "slot", "valid")]
 
 
+class BpRolloutDesc(C.Structure):
+    _fields_ = [("n_steps", C.c_int32), ("num_envs", C.c_int32), ("device", C.c_int32), ("action_dim", C.c_int32), ("row_bytes", C.c_int64)] + \
+               [(n, C.c_void_p) for n in ("obs", "action", "reward", "value", "logp", "advantage", "ret", "episode_start", "last_done", "hdr")]
+
+
+class BpRolloutBatch(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("obs", "action", "value", "logp", "advantage", "ret", "index", "valid")]
+
+
 class BpLatticeConfig(C.Structure):
     _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("S", C.c_int32), ("nh", C.c_int32), ("nb", C.c_int32), ("ne_max", C.c_int32), ("den", C.c_int32),
                 ("margin", C.c_int32), ("h_baseline", C.c_int32), ("max_expansions", C.c_int32), ("node_capacity", C.c_int32),
@@ -187,6 +196,12 @@ def _abi():
             "bp_replay_index": (i64, [u64, i64, i32, i64]), "bp_replay_observe": (I, [P(BpReplayDesc)] + [vp] * 7 + [i32, i32, vp]),
             "bp_replay_record": (I, [P(BpReplayDesc), vp, vp, vp, i32, vp]),
             "bp_replay_sample": (I, [P(BpReplayDesc), i32, u64, P(BpReplayBatch), vp])},
+        "bp_rollout_begin": {   # on-policy rollout buffer with GAE
+            "bp_rollout_index": (i64, [u64, i64, i64, i64]), "bp_rollout_begin": (I, [P(BpRolloutDesc), i32, vp, vp, vp, vp, vp]),
+            "bp_rollout_pick_rows": (I, [P(BpRolloutDesc), vp, vp, i32, vp, vp, vp]),
+            "bp_rollout_end": (I, [P(BpRolloutDesc), i32, vp, vp, vp, vp, i32, f64, vp]),
+            "bp_rollout_finish": (I, [P(BpRolloutDesc), vp, f64, f64, vp]),
+            "bp_rollout_minibatch": (I, [P(BpRolloutDesc), u64, i64, i32, i32, P(BpRolloutBatch), vp])},
     }
     # (sizeof function, the struct it measures, group, the error when the two disagree); the functions join their groups in the table
     layouts = [("bp_sizeof_config", BpConfig, None, "bp_config layout mismatch between _lib.BpConfig and the library"),
@@ -200,7 +215,9 @@ def _abi():
                ("bp_sizeof_track_wp_config", BpTrackWpConfig, "bp_rrt_plan", "bp_rrt_config / bp_track_wp_config layout mismatch between _lib and the library"),
                ("bp_sizeof_gtsp_config", BpGtspConfig, "bp_gtsp_plan", "bp_gtsp_config layout mismatch between _lib.BpGtspConfig and the library"),
                ("bp_sizeof_replay_desc", BpReplayDesc, "bp_replay_observe", "bp_replay_desc / bp_replay_batch layout mismatch between _lib and the library"),
-               ("bp_sizeof_replay_batch", BpReplayBatch, "bp_replay_observe", "bp_replay_desc / bp_replay_batch layout mismatch between _lib and the library")]
+               ("bp_sizeof_replay_batch", BpReplayBatch, "bp_replay_observe", "bp_replay_desc / bp_replay_batch layout mismatch between _lib and the library"),
+               ("bp_sizeof_rollout_desc", BpRolloutDesc, "bp_rollout_begin", "bp_rollout_desc / bp_rollout_batch layout mismatch between _lib and the library"),
+               ("bp_sizeof_rollout_batch", BpRolloutBatch, "bp_rollout_begin", "bp_rollout_desc / bp_rollout_batch layout mismatch between _lib and the library")]
     table = {name: decl + (group,) for group, fns in groups.items() for name, decl in fns.items()}
     table.update((name, (i32, [], group)) for name, _, group, _ in layouts)
     # entry points of the library that the header does not declare: the diagnostic twins' hooks (tools/, tests of the twins)

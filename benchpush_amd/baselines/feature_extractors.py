@@ -1,11 +1,18 @@
 """Networks of the learning baselines.  ``DenseActionSpaceDQN`` is the fully convolutional Q-network of the spatial-action-map baseline (SAM): one Q value
 per pixel of the observation.  Written from its description; the parameter names are the reference's (benchpush/baselines/feature_extractors.py), so a
 checkpoint trained there loads here with ``load_state_dict(strict=True)`` (tests/golden/sam_state_dict.json pins names, shapes and one float64 output).
+
+``ResNet18Extractor`` and ``ActorCriticCnn`` are the networks of the PPO baselines (benchpush_amd/baselines/ppo.py).  The reference builds them from
+torchvision's ``resnet18`` and stable-baselines3's ``ActorCriticCnnPolicy``; neither package is available to this project's build, so the parameter
+names below are argued from the documented structure of the two and are not pinned by a fixture of the reference.
 """
+import math
+
+import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-__all__ = ["DenseActionSpaceDQN", "ResNet18NoNorm", "ResidualBlock"]
+__all__ = ["ActorCriticCnn", "BasicBlockBN", "DenseActionSpaceDQN", "ResNet18Extractor", "ResNet18NoNorm", "ResidualBlock"]
 
 
 class ResidualBlock(nn.Module):
@@ -67,3 +74,102 @@ class DenseActionSpaceDQN(nn.Module):
         for conv in (self.conv1, self.conv2):
             x = F.interpolate(F.relu(conv(x)), scale_factor=2, mode="bilinear", align_corners=True)
         return self.conv3(x)
+
+
+class BasicBlockBN(nn.Module):
+    """The stock ResNet basic block: 3x3 convolution (stride `stride`), batch norm, ReLU, 3x3 convolution, batch norm, plus the input (through
+    `downsample`, a 1x1 stride-`stride` convolution with batch norm, where the shape changes), ReLU."""
+
+    def __init__(self, width_in, width, stride=1):
+        super().__init__()
+        self.conv1 = nn.Conv2d(width_in, width, 3, stride=stride, padding=1, bias=False)
+        self.bn1 = nn.BatchNorm2d(width)
+        self.relu = nn.ReLU(inplace=True)
+        self.conv2 = nn.Conv2d(width, width, 3, padding=1, bias=False)
+        self.bn2 = nn.BatchNorm2d(width)
+        self.downsample = None
+        if stride != 1 or width_in != width:
+            self.downsample = nn.Sequential(nn.Conv2d(width_in, width, 1, stride=stride, bias=False), nn.BatchNorm2d(width))
+
+    def forward(self, x):
+        skip = x if self.downsample is None else self.downsample(x)
+        return self.relu(self.bn2(self.conv2(self.relu(self.bn1(self.conv1(x))))) + skip)
+
+
+class ResNet18Extractor(nn.Module):
+    """[N, C, H, W] -> [N, 512]: the stock ResNet-18 with batch norm and stride-2 stages, a stem for the env's channel count (7x7 stride-2 convolution
+    without bias, like the stock stem it replaces), global average pooling instead of the classifier.  ``resnet`` is an
+    ``nn.Sequential`` whose children stand in the stock model's order -- 0 stem convolution, 1 its batch norm, 2 ReLU, 3 max-pool, 4 .. 7 the stages, 8
+    the average pool -- so the parameters are called ``resnet.0.weight``, ``resnet.1.running_mean``, ``resnet.4.0.conv1.weight``,
+    ``resnet.5.0.downsample.0.weight`` and so on."""
+
+    WIDTHS = (64, 128, 256, 512)
+
+    def __init__(self, num_input_channels=4, features_dim=512):
+        super().__init__()
+        if features_dim != 512:
+            raise ValueError("ResNet18Extractor: the trunk gives 512 features")
+        self.features_dim = 512
+        layers = [nn.Conv2d(num_input_channels, 64, 7, stride=2, padding=3, bias=False), nn.BatchNorm2d(64), nn.ReLU(inplace=True), nn.MaxPool2d(3, stride=2, padding=1)]
+        width_in = 64
+        for i, width in enumerate(self.WIDTHS):
+            layers.append(nn.Sequential(BasicBlockBN(width_in, width, stride=1 if i == 0 else 2), BasicBlockBN(width, width)))
+            width_in = width
+        layers.append(nn.AdaptiveAvgPool2d((1, 1)))
+        self.resnet = nn.Sequential(*layers)
+
+    def forward(self, x):
+        return torch.flatten(self.resnet(x), 1)
+
+
+class _MlpExtractor(nn.Module):
+    def __init__(self, features_dim, pi, vf):
+        super().__init__()
+
+        def net(widths):
+            layers, w_in = [], features_dim
+            for w in widths:
+                layers += [nn.Linear(w_in, w), nn.Tanh()]
+                w_in = w
+            return nn.Sequential(*layers)
+        self.policy_net, self.value_net = net(pi), net(vf)
+        self.latent_dim_pi, self.latent_dim_vf = pi[-1], vf[-1]
+
+
+class ActorCriticCnn(nn.Module):
+    """Gaussian actor-critic on image observations, laid out as stable-baselines3's ``ActorCriticCnnPolicy`` with the reference's arguments
+    (features_extractor_class ResNet18, net_arch pi = vf = [512, 256]): ``features_extractor`` (shared by actor and critic),
+    ``mlp_extractor.policy_net`` and ``mlp_extractor.value_net`` (512 -> 512 -> 256 with tanh: Linear layers 0 and 2 of each), ``action_net``
+    (256 -> action_dim, the mean), ``value_net`` (256 -> 1) and a state-independent ``log_std`` (zeros).  Linear and convolution weights start
+    orthogonal with gain sqrt(2) (``action_net`` 0.01, ``value_net`` 1) and zero bias, as that policy's ``ortho_init`` does.  stable-baselines3 2.x
+    also registers the shared extractor as ``pi_features_extractor`` and ``vf_features_extractor``; a checkpoint of its policy carries those duplicate
+    keys, which ``load_state_dict(strict=False)`` skips.  Observations are float [N, C, H, W] in [0, 1] (uint8 / 255)."""
+
+    def __init__(self, num_input_channels=4, action_dim=1, net_arch=None):
+        super().__init__()
+        arch = net_arch or dict(pi=[512, 256], vf=[512, 256])
+        self.action_dim = int(action_dim)
+        self.features_extractor = ResNet18Extractor(num_input_channels)
+        self.mlp_extractor = _MlpExtractor(512, list(arch["pi"]), list(arch["vf"]))
+        self.action_net = nn.Linear(self.mlp_extractor.latent_dim_pi, self.action_dim)
+        self.value_net = nn.Linear(self.mlp_extractor.latent_dim_vf, 1)
+        self.log_std = nn.Parameter(torch.zeros(self.action_dim))
+        for module, gain in ((self.features_extractor, math.sqrt(2)), (self.mlp_extractor, math.sqrt(2)), (self.action_net, 0.01), (self.value_net, 1.0)):
+            for m in module.modules():
+                if isinstance(m, (nn.Linear, nn.Conv2d)):
+                    nn.init.orthogonal_(m.weight, gain=gain)
+                    if m.bias is not None:
+                        m.bias.data.fill_(0.0)
+
+    def forward(self, obs):
+        """(mean [N, A], value [N])."""
+        f = self.features_extractor(obs)
+        return self.action_net(self.mlp_extractor.policy_net(f)), self.value_net(self.mlp_extractor.value_net(f)).squeeze(1)
+
+    def value(self, obs):
+        return self.value_net(self.mlp_extractor.value_net(self.features_extractor(obs))).squeeze(1)
+
+    def log_prob(self, mean, actions):
+        """log N(actions; mean, exp(log_std)) summed over the action columns, [N]."""
+        var = torch.exp(2.0 * self.log_std)
+        return (-((actions - mean) ** 2) / (2.0 * var) - self.log_std - 0.5 * math.log(2.0 * math.pi)).sum(dim=1)

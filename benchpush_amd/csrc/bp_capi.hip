@@ -28,6 +28,7 @@
 #include "bp_gtsp.hpp"
 #include "bp_asyncq.hpp"
 #include "bp_replay.hpp"
+#include "bp_rollout.hpp"
 
 // The kernels of a ship-ice / maze handle, one per role, chosen once at load (rigid_kernels): the 8-vertex maze instantiations, the generic pair of a
 // handle with damping (no scheduler), or the ship-ice ones.
@@ -2655,6 +2656,99 @@ int bp_replay_sample(const bp_replay_desc *d, int32_t B, uint64_t seed, const bp
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_replay_pick, dim3(1), dim3(RPL_THREADS), 0, st, r, o, B, (unsigned long long)seed);
     hipLaunchKernelGGL(k_replay_gather, dim3(B, replay_pieces(r)), dim3(RPL_COPY_THREADS), 0, st, r, o);
+    return hipGetLastError() == hipSuccess ? BP_OK : BP_EHIP;
+}
+
+// ---- on-policy rollout buffer with GAE (bp_rollout.hpp): handle-free, the caller owns the memory ----
+int32_t bp_sizeof_rollout_desc(void) { return (int32_t)sizeof(bp_rollout_desc); }
+int32_t bp_sizeof_rollout_batch(void) { return (int32_t)sizeof(bp_rollout_batch); }
+int64_t bp_rollout_index(uint64_t seed, int64_t epoch, int64_t i, int64_t n)
+{
+    if (n < 1 || n > 0x7FFFFFFFll || i < 0 || i >= n) return -1;
+    return bp_rollout_perm(seed, epoch, i, n);
+}
+static int rollout_strips(const RolloutBuf &r)
+{
+    const int pieces = (r.row16 + RPL_COPY_THREADS - 1) / RPL_COPY_THREADS;
+    return pieces < RLO_ROW_STRIPS ? pieces : RLO_ROW_STRIPS;
+}
+static int rollout_buf(const bp_rollout_desc *d, RolloutBuf *r)
+{
+    if (!d || !d->obs || !d->action || !d->reward || !d->value || !d->logp || !d->advantage || !d->ret || !d->episode_start || !d->last_done || !d->hdr)
+        return BP_EINVAL;
+    if (d->n_steps < 1 || d->num_envs < 1 || d->action_dim < 1 || d->device < 0) return BP_EINVAL;
+    if ((int64_t)d->n_steps * d->num_envs > 0x7FFFFFFFll || (int64_t)d->num_envs * d->action_dim > 0x7FFFFFFFll) return BP_EINVAL;
+    if (d->row_bytes < 16 || d->row_bytes % 16 != 0 || d->row_bytes / 16 > 0x7FFFFFFFll) return BP_EINVAL;
+    if ((((uintptr_t)d->obs) & 15u) != 0) return BP_EINVAL;
+    r->T = d->n_steps; r->E = d->num_envs; r->A = d->action_dim; r->row16 = (int)(d->row_bytes / 16);
+    r->obs = (uint4 *)d->obs; r->action = d->action; r->reward = d->reward; r->value = d->value; r->logp = d->logp; r->advantage = d->advantage;
+    r->ret = d->ret; r->episode_start = d->episode_start; r->last_done = d->last_done; r->hdr = (long long *)d->hdr;
+    return BP_OK;
+}
+int bp_rollout_begin(const bp_rollout_desc *d, int32_t t, const uint8_t *obs, const float *action, const float *value, const float *logp, void *stream)
+{
+    RolloutBuf r;
+    if (rollout_buf(d, &r) != BP_OK || !obs || !action || !value || !logp || t < 0 || t >= d->n_steps || (((uintptr_t)obs) & 15u) != 0) return BP_EINVAL;
+    DevGuard dg(d->device);
+    if (!dg.ok) return BP_EHIP;
+    int64_t n = (int64_t)r.E * r.row16;               // pieces of the batch; E * A and E threads ride along
+    if ((int64_t)r.E * r.A > n) n = (int64_t)r.E * r.A;
+    int64_t blocks = (n + RPL_COPY_THREADS - 1) / RPL_COPY_THREADS;
+    if (blocks > RLO_COPY_BLOCKS) blocks = RLO_COPY_BLOCKS;
+    hipLaunchKernelGGL(k_rollout_begin, dim3((unsigned)blocks), dim3(RPL_COPY_THREADS), 0, (hipStream_t)stream, r, (int)t, (const uint4 *)obs, action, value, logp);
+    return hipGetLastError() == hipSuccess ? BP_OK : BP_EHIP;
+}
+int bp_rollout_pick_rows(const bp_rollout_desc *d, const uint8_t *mask, const uint8_t *src, int32_t K, int32_t *out_ids, float *out_rows, void *stream)
+{
+    RolloutBuf r;
+    if (rollout_buf(d, &r) != BP_OK || !mask || !src || !out_ids || !out_rows || K < 1) return BP_EINVAL;
+    if (((((uintptr_t)src) | ((uintptr_t)out_rows)) & 15u) != 0) return BP_EINVAL;
+    DevGuard dg(d->device);
+    if (!dg.ok) return BP_EHIP;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_rollout_pick, dim3(1), dim3(RPL_THREADS), 0, st, r, (const unsigned char *)mask, (int)K, (int *)out_ids);
+    hipLaunchKernelGGL(k_rollout_rows, dim3(K, rollout_strips(r)), dim3(RPL_COPY_THREADS), 0, st, (const uint4 *)src, (const int *)out_ids,
+                       (const unsigned char *)nullptr, (long long)r.E, r.row16, out_rows);
+    return hipGetLastError() == hipSuccess ? BP_OK : BP_EHIP;
+}
+int bp_rollout_end(const bp_rollout_desc *d, int32_t t, const double *reward, const uint8_t *done, const int32_t *boot_ids, const float *boot_values,
+                   int32_t K, double gamma, void *stream)
+{
+    RolloutBuf r;
+    if (rollout_buf(d, &r) != BP_OK || !reward || !done || t < 0 || t >= d->n_steps) return BP_EINVAL;
+    if (boot_ids && (!boot_values || K < 1)) return BP_EINVAL;
+    DevGuard dg(d->device);
+    if (!dg.ok) return BP_EHIP;
+    hipLaunchKernelGGL(k_rollout_end, dim3(1), dim3(RPL_THREADS), 0, (hipStream_t)stream, r, (int)t, reward, (const unsigned char *)done,
+                       (const int *)boot_ids, boot_values, boot_ids ? (int)K : 0, (float)gamma);
+    return hipGetLastError() == hipSuccess ? BP_OK : BP_EHIP;
+}
+int bp_rollout_finish(const bp_rollout_desc *d, const float *last_values, double gamma, double gl, void *stream)
+{
+    RolloutBuf r;
+    if (rollout_buf(d, &r) != BP_OK || !last_values) return BP_EINVAL;
+    DevGuard dg(d->device);
+    if (!dg.ok) return BP_EHIP;
+    hipLaunchKernelGGL(k_rollout_gae, dim3((r.E + RLO_GAE_THREADS - 1) / RLO_GAE_THREADS), dim3(RLO_GAE_THREADS), 0, (hipStream_t)stream, r, last_values,
+                       (float)gamma, (float)gl);
+    return hipGetLastError() == hipSuccess ? BP_OK : BP_EHIP;
+}
+int bp_rollout_minibatch(const bp_rollout_desc *d, uint64_t seed, int64_t epoch, int32_t j, int32_t B, const bp_rollout_batch *out, void *stream)
+{
+    RolloutBuf r;
+    if (rollout_buf(d, &r) != BP_OK || !out || B < 1 || j < 0 || (int64_t)j * B >= (int64_t)d->n_steps * d->num_envs) return BP_EINVAL;
+    if (!out->obs || !out->action || !out->value || !out->logp || !out->advantage || !out->ret || !out->index || !out->valid) return BP_EINVAL;
+    if ((((uintptr_t)out->obs) & 15u) != 0) return BP_EINVAL;
+    RolloutBatch o;
+    o.obs = out->obs; o.action = out->action; o.value = out->value; o.logp = out->logp; o.advantage = out->advantage; o.ret = out->ret;
+    o.index = out->index; o.valid = out->valid;
+    DevGuard dg(d->device);
+    if (!dg.ok) return BP_EHIP;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_rollout_index, dim3((B + RPL_COPY_THREADS - 1) / RPL_COPY_THREADS), dim3(RPL_COPY_THREADS), 0, st, r, o, (unsigned long long)seed,
+                       (long long)epoch, (long long)j * B, (int)B);
+    hipLaunchKernelGGL(k_rollout_rows, dim3(B, rollout_strips(r)), dim3(RPL_COPY_THREADS), 0, st, (const uint4 *)r.obs, (const int *)o.index,
+                       (const unsigned char *)o.valid, (long long)r.T * r.E, r.row16, o.obs);
     return hipGetLastError() == hipSuccess ? BP_OK : BP_EHIP;
 }
 

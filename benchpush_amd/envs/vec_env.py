@@ -81,6 +81,16 @@ class LazyInfos(collections.abc.Sequence):
             self._cache[i] = d
         return d
 
+    @property
+    def truncated_mask(self):
+        """The step's ``TimeLimit.truncated`` flags of all envs, [E] (a device tensor with ``to_numpy=False``), as held: nothing is copied."""
+        return self._trunc
+
+    @property
+    def terminal_rows(self):
+        """The terminal observations [E, ...]; only the rows of the envs whose episode ended in this step are this step's (same lifetime as ``infos[i]``)."""
+        return self._term_obs
+
     def done_indices(self):
         """Host indices of the envs whose episode ended in this step (one small copy)."""
         return np.nonzero(self._pull()[1])[0]

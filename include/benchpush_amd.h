@@ -793,6 +793,65 @@ int bp_replay_observe(const bp_replay_desc *d, const int32_t *ids, const uint8_t
 int bp_replay_record(const bp_replay_desc *d, const double *actions, const int32_t *ids, const uint8_t *reset, int32_t M, void *stream);
 int bp_replay_sample(const bp_replay_desc *d, int32_t B, uint64_t seed, const bp_replay_batch *out, void *stream);
 
+/* ---- on-policy rollout buffer with GAE (DESIGN.md "Rollout buffer") ----
+ * Handle-free: the caller owns every array (device memory on `device`) and passes them in a bp_rollout_desc.  T = n_steps, E = num_envs, A = action_dim,
+ * R = row_bytes (a multiple of 16; the rows are uint8 and their shape is opaque to the library; every observation array is 16-byte aligned), N = T * E
+ * (at most 2^31 - 1).
+ *   obs uint8 [T][E][R]; action float [T][E][A]; reward, value, logp, advantage, ret float [T][E]; episode_start uint8 [T][E]; last_done uint8 [E]
+ *   hdr int64 [2]: hdr[0] truncated rows left without a bootstrap, hdr[1] rows stored (E per bp_rollout_end)
+ * All of it starts as zeros.  The step index t, the epoch and the minibatch number are host integers: the call sequence does not depend on data.
+ *
+ * bp_rollout_begin, before the env step: obs[t] = the [E][R] batch the policy acted on (the env rewrites its buffer in place), action[t], value[t],
+ * logp[t] = the float [E][A] / [E] / [E] arguments, episode_start[t] = last_done.
+ *
+ * bp_rollout_pick_rows: the first K envs in ascending order with mask[e] != 0: out_ids[k] = e and out_rows[k] = (float)src[e][.] / 255.0f as float [K][R]
+ * (an IEEE division, not a reciprocal); rows beyond the number found get out_ids = -1 and zeros; hdr[0] += the number of masked envs beyond K.  This is the
+ * fixed-size batch on which the policy evaluates V(terminal observation) of the truncated envs without a host read.  src uint8 [E][R], out_rows 16-byte aligned.
+ *
+ * bp_rollout_end, after the env step: reward[t][e] = (float)reward[e] (reward is double [E]); then for every k < K with boot_ids[k] = e in [0, E):
+ * reward[t][e] = reward[t][e] + (float)gamma * boot_values[k] (the ids >= 0 of one call must be distinct, as bp_rollout_pick_rows makes them; boot_ids may
+ * be NULL, K is then not read); last_done = done (uint8 [E]); hdr[1] += E.
+ *
+ * bp_rollout_finish, the GAE scan backwards over t, all in float, in exactly this order (g = (float)gamma; gl = (float)gl, the caller computes
+ * (double)gamma * (double)lambda): nn = 1 - done_next; delta = (reward[t] + (g * v_next) * nn) - value[t]; adv = delta + (gl * nn) * adv;
+ * advantage[t] = adv; ret[t] = adv + value[t].  For t = T - 1, v_next and done_next are last_values (float [E]) and last_done, otherwise value[t + 1] and
+ * episode_start[t + 1]; adv starts at 0.
+ *
+ * bp_rollout_minibatch: sample b of minibatch j takes the flat index i = bp_rollout_index(seed, epoch, j * B + b, N), t = i / E, e = i % E, and writes
+ * out->obs float [B][R] ((float)u8 / 255.0f by IEEE division, 16-byte aligned), action float [B][A], value, logp, advantage, ret float [B], index int32 [B],
+ * valid uint8 [B]; samples with j * B + b >= N have valid = 0 and zeros everywhere.  j * B < N.
+ *
+ * bp_rollout_index is a host function, the kernel's rule: a keyed bijection of [0, N), so an epoch visits every stored transition exactly once.  It is a
+ * 4-round balanced Feistel network over 2h bits, h the smallest value with 4^h >= N: x = i; (left, right) = (x >> h, x & (2^h - 1)); round r = 0 .. 3 maps
+ * (left, right) to (right, left ^ F) with F = the low h bits of S[key ^ (r << 32 | right)] >> 32, key = S[seed ^ S[epoch]], S the splitmix64 step of the
+ * project's counter RNG (the one bp_replay_index and bp_rrt_uniform use); x = left << h | right; repeated while x >= N (cycle walking: the network permutes the
+ * 2h-bit domain, so this ends).  -1 for N outside 1 .. 2^31 - 1 or i outside [0, N).
+ *
+ * Nothing synchronises, nothing is read back; all work is enqueued on `stream`.  BP_EINVAL, before anything is launched: a NULL pointer (boot_ids excepted),
+ * row_bytes % 16 != 0, n_steps, num_envs or action_dim < 1, t outside [0, T), K or B < 1, j * B outside [0, N).  (Added within ABI 11: the additions only add.) */
+typedef struct bp_rollout_desc {
+    int32_t n_steps, num_envs, device, action_dim;
+    int64_t row_bytes;
+    uint8_t *obs;
+    float *action, *reward, *value, *logp, *advantage, *ret;
+    uint8_t *episode_start, *last_done;
+    int64_t *hdr;
+} bp_rollout_desc;
+typedef struct bp_rollout_batch {
+    float *obs, *action, *value, *logp, *advantage, *ret;
+    int32_t *index;
+    uint8_t *valid;
+} bp_rollout_batch;
+int32_t bp_sizeof_rollout_desc(void);
+int32_t bp_sizeof_rollout_batch(void);
+int64_t bp_rollout_index(uint64_t seed, int64_t epoch, int64_t i, int64_t n);
+int bp_rollout_begin(const bp_rollout_desc *d, int32_t t, const uint8_t *obs, const float *action, const float *value, const float *logp, void *stream);
+int bp_rollout_pick_rows(const bp_rollout_desc *d, const uint8_t *mask, const uint8_t *src, int32_t K, int32_t *out_ids, float *out_rows, void *stream);
+int bp_rollout_end(const bp_rollout_desc *d, int32_t t, const double *reward, const uint8_t *done, const int32_t *boot_ids, const float *boot_values,
+                   int32_t K, double gamma, void *stream);
+int bp_rollout_finish(const bp_rollout_desc *d, const float *last_values, double gamma, double gl, void *stream);
+int bp_rollout_minibatch(const bp_rollout_desc *d, uint64_t seed, int64_t epoch, int32_t j, int32_t B, const bp_rollout_batch *out, void *stream);
+
 const char *bp_last_error(const bp_handle *h);
 int32_t bp_abi_version(void);
 int32_t bp_sizeof_config(void);   /* sizeof(bp_config), so a binding can verify its struct layout */
