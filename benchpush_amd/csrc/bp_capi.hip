@@ -16,7 +16,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
-#include "bp_host_bd.hpp"
+#include "bp_host_scene.hpp"
 #include "bp_boxdelivery.hpp"
 #include "bp_policy.hpp"
 #include "bp_render.hpp"
@@ -370,53 +370,10 @@ int bp_destroy(bp_handle *h)
 }
 
 // ---- the scenario loader (upload_trials) as a sequence of steps ----------------------------------------------------------------------------------
-// Step 1: the per-trial bodies as SoA tables with nbcap slots per trial, and the scenario hash over them.
-struct TrialTables {
-    std::vector<int> nb, nv, kind;
-    std::vector<d2> lv, ln;
-    std::vector<double4> mass, pose, prop;
-};
-static int pack_trials(bp_handle *h, const std::vector<std::vector<bpgeom::Shape>> &trials, int nbcap, TrialTables &tt)
-{
-    using namespace bpgeom;
-    const int T = (int)trials.size();
-    tt.nb.assign(T, 0); tt.nv.assign((size_t)T * nbcap, 0); tt.kind.assign((size_t)T * nbcap, 0);
-    tt.lv.resize((size_t)T * nbcap * BP_MAXV); tt.ln.resize((size_t)T * nbcap * BP_MAXV);
-    tt.mass.resize((size_t)T * nbcap); tt.pose.resize((size_t)T * nbcap); tt.prop.resize((size_t)T * nbcap);
-    memset(tt.lv.data(), 0, tt.lv.size() * sizeof(d2));
-    memset(tt.ln.data(), 0, tt.ln.size() * sizeof(d2));
-    memset(tt.mass.data(), 0, tt.mass.size() * sizeof(double4));
-    memset(tt.pose.data(), 0, tt.pose.size() * sizeof(double4));
-    memset(tt.prop.data(), 0, tt.prop.size() * sizeof(double4));
-    for (int t = 0; t < T; t++) {
-        tt.nb[t] = (int)trials[t].size();
-        for (int b = 0; b < (int)trials[t].size(); b++) {
-            const Shape &s = trials[t][b];
-            if ((int)s.verts.size() > BP_MAXV) return fail(h, BP_EINVAL, "hull exceeds BP_MAXV vertices");
-            const size_t o = (size_t)t * nbcap + b;
-            tt.nv[o] = (int)s.verts.size();
-            for (int i = 0; i < (int)s.verts.size(); i++) {
-                tt.lv[o * BP_MAXV + i].x = s.verts[i].x; tt.lv[o * BP_MAXV + i].y = s.verts[i].y;
-                tt.ln[o * BP_MAXV + i].x = s.normals[i].x; tt.ln[o * BP_MAXV + i].y = s.normals[i].y;
-            }
-            tt.mass[o].x = s.m_inv; tt.mass[o].y = s.i_inv; tt.mass[o].z = s.cog.x; tt.mass[o].w = s.cog.y;
-            tt.pose[o].x = s.p.x; tt.pose[o].y = s.p.y; tt.pose[o].z = s.angle; tt.pose[o].w = 0.0;
-            tt.prop[o].x = s.radius; tt.prop[o].y = s.e; tt.prop[o].z = s.u; tt.prop[o].w = 0.0;
-            tt.kind[o] = s.kind;
-        }
-    }
-    // scenario hash of the state records' layout id: the tables exactly as they are uploaded
-    unsigned long long sh = h->scen_hash;
-    sh = bp_fnv1a(tt.nb.data(), sizeof(int) * tt.nb.size(), sh); sh = bp_fnv1a(tt.nv.data(), sizeof(int) * tt.nv.size(), sh);
-    sh = bp_fnv1a(tt.kind.data(), sizeof(int) * tt.kind.size(), sh);
-    sh = bp_fnv1a(tt.lv.data(), sizeof(d2) * tt.lv.size(), sh); sh = bp_fnv1a(tt.ln.data(), sizeof(d2) * tt.ln.size(), sh);
-    sh = bp_fnv1a(tt.mass.data(), sizeof(double4) * tt.mass.size(), sh); sh = bp_fnv1a(tt.pose.data(), sizeof(double4) * tt.pose.size(), sh);
-    sh = bp_fnv1a(tt.prop.data(), sizeof(double4) * tt.prop.size(), sh);
-    h->scen_hash = sh;
-    return BP_OK;
-}
+// Step 1 is host-only: bpgeom::pack_trials (bp_host_scene.hpp), the per-trial bodies as SoA tables with nbcap slots per trial and the scenario hash over them.
 // Step 2: the tables to the device (upload_tables)
-static int upload_trial_tables(bp_handle *h, const TrialTables &tt)
+static_assert(sizeof(bpgeom::P2) == sizeof(d2) && sizeof(bpgeom::D4) == sizeof(double4), "the host tables are uploaded as d2 / double4");
+static int upload_trial_tables(bp_handle *h, const bpgeom::TrialTables &tt)
 {
     DevTable tab[8] = {dev_table(tt.nb), dev_table(tt.nv), dev_table(tt.kind), dev_table(tt.lv), dev_table(tt.ln), dev_table(tt.mass), dev_table(tt.pose), dev_table(tt.prop)};
     if (int rc = upload_tables(h, tab, 8)) return rc;
@@ -593,7 +550,7 @@ static int sched_setup(bp_handle *h, bool maze)
     return h->P.pair_mode == 2 ? pair_resident_setup(h) : sched_persist_setup(h);
 }
 // The plan of a ship-ice handle without damping: pairing mode, then the scheduler.
-static int ship_plan(bp_handle *h, const std::vector<std::vector<bpgeom::Shape>> &trials)
+static int ship_plan(bp_handle *h, const bpgeom::Trials &trials)
 {
     const int T = (int)trials.size(), nbcap = h->nbcap;
     bool plain = true; // one kinematic shape (index 0), dynamic shapes without groups otherwise
@@ -647,13 +604,11 @@ static int settle_templates(bp_handle *h)
 }
 // Common tail of the scenario loaders: SoA upload of the per-trial bodies, per-env state allocation, the launch plan, and one settle of
 // every trial into its reset template (state slot num_envs + t).  bp_bd_load passes settle = false: it plans and settles on its own.
-static int upload_trials(bp_handle *h, const std::vector<std::vector<bpgeom::Shape>> &trials, bool settle = true)
+static int upload_trials(bp_handle *h, const bpgeom::Trials &trials, bool settle = true)
 {
     const int T = (int)trials.size();
-    int maxnb = 1;
-    for (const auto &b : trials) maxnb = std::max(maxnb, (int)b.size());
-    if (maxnb > 60000) return fail(h, BP_EINVAL, "too many bodies");
-    const int nbcap = (maxnb + 7) / 8 * 8;
+    const int nbcap = bpgeom::trials_nbcap(trials);
+    if (nbcap > 60000) return fail(h, BP_EINVAL, "too many bodies");
     h->nbcap = nbcap;
     h->num_trials = T;
     h->P.nbcap = nbcap;
@@ -664,8 +619,8 @@ static int upload_trials(bp_handle *h, const std::vector<std::vector<bpgeom::Sha
     // the candidate cache (LdsCtx::cc, bp_physics.hpp step 3) packs both body indices of a pair into BP_CC_IDX_BITS bits each
     if (nbcap >= (1 << BP_CC_IDX_BITS)) return fail(h, BP_EINVAL, "nb_cap exceeds the candidate cache's body-index field (16384 bodies per env)");
     int rc;
-    TrialTables tt;
-    if ((rc = pack_trials(h, trials, nbcap, tt))) return rc;
+    bpgeom::TrialTables tt;
+    if (const char *e = bpgeom::pack_trials(trials, nbcap, tt, h->scen_hash)) return fail(h, BP_EINVAL, e);
     if ((rc = upload_trial_tables(h, tt))) return rc;
     if ((rc = alloc_env_state(h, T))) return rc;
     HIPCHK(h, hipDeviceSynchronize());
@@ -711,8 +666,7 @@ static int state_setup(bp_handle *h)
     return BP_OK;
 }
 
-static int kind_of(int ctype, int group, int btype) { return ctype | (group << 8) | (btype << 16); }
-
+// The loaders: argument and state checks, the host-only scene builder (bp_host_scene.hpp), then the device steps.
 int bp_load_scenarios(bp_handle *h, int32_t T, int32_t F, int32_t V, const double *verts, const int32_t *counts,
                       const double *centres, const double *starts, const int32_t *nfloes)
 {
@@ -720,29 +674,8 @@ int bp_load_scenarios(bp_handle *h, int32_t T, int32_t F, int32_t V, const doubl
     if (h->loaded) return fail(h, BP_ESTATE, "scenarios already loaded");
     if (h->P.env_kind != BP_ENV_SHIP_ICE) return fail(h, BP_ESTATE, "handle was created for another environment");
     BP_DEVICE(h);
-    using namespace bpgeom;
-    std::vector<std::vector<Shape>> trials(T);
-    for (int t = 0; t < T; t++) {
-        std::vector<Shape> &bodies = trials[t];
-        Shape ship;
-        build_ship(h->cfg.ship_verts, h->cfg.num_ship_verts, starts[3 * t], starts[3 * t + 1], starts[3 * t + 2], ship);
-        ship.radius = h->cfg.poly_radius; ship.e = h->cfg.elasticity; ship.u = h->cfg.friction;
-        ship.kind = kind_of(1, 0, BODY_KINEMATIC); // ship_ice_env.py:214-215
-        bodies.push_back(ship);
-        if (nfloes[t] > F) return fail(h, BP_EINVAL, "nfloes > F");
-        for (int f = 0; f < nfloes[t]; f++) {
-            const int n = counts[(size_t)t * F + f];
-            if (n < 3) continue;
-            if (n > V) return fail(h, BP_EINVAL, "vertex count > V");
-            Shape s;
-            if (!build_floe(verts + ((size_t)t * F + f) * V * 2, n, centres[((size_t)t * F + f) * 2],
-                            centres[((size_t)t * F + f) * 2 + 1], h->cfg.density, h->cfg.poly_radius, s))
-                continue;
-            s.radius = h->cfg.poly_radius; s.e = h->cfg.elasticity; s.u = h->cfg.friction;
-            s.kind = kind_of(2, 0, BODY_DYNAMIC);  // ship_ice_env.py:211-212
-            bodies.push_back(s);
-        }
-    }
+    bpgeom::Trials trials;
+    if (const char *e = bpgeom::ship_ice_scene(h->cfg, T, F, V, verts, counts, centres, starts, nfloes, trials)) return fail(h, BP_EINVAL, e);
     const int rc_up = upload_trials(h, trials);
     return rc_up ? rc_up : state_setup(h);
 }
@@ -753,61 +686,21 @@ int bp_load_maze(bp_handle *h, int32_t T, int32_t nbox, const double *centres, i
     if (h->loaded) return fail(h, BP_ESTATE, "scenarios already loaded");
     if (h->P.env_kind != BP_ENV_MAZE) return fail(h, BP_ESTATE, "handle was created for another environment");
     BP_DEVICE(h);
-    using namespace bpgeom;
-    const bp_config &cf = h->cfg;
-    std::vector<std::vector<Shape>> trials(T);
-    for (int t = 0; t < T; t++) {
-        std::vector<Shape> &bodies = trials[t];
-        // robot: one KINEMATIC body with the main outline (type 1) + the wheels (type 0); friction stays at pymunk's
-        // default 0 (Robot.sim sets mass and elasticity only, robot.py:90-105)
-        for (int k = 0; k <= cf.num_wheels; k++) {
-            Shape s;
-            const double *st3 = start + 3 * (size_t)t;   // start pose of this layout (maze_NAMO_env.py:229-245)
-            if (k == 0) build_kinematic_part(cf.ship_verts, cf.num_ship_verts, st3[0], st3[1], st3[2], s);
-            else build_kinematic_part(cf.wheel_verts[k - 1], 4, st3[0], st3[1], st3[2], s);
-            s.radius = cf.poly_radius; s.e = cf.elasticity; s.u = 0.0;
-            s.kind = kind_of(k == 0 ? 1 : 0, 1, BODY_KINEMATIC);
-            bodies.push_back(s);
-        }
-        for (int b = 0; b < nbox; b++) {
-            const double ox = centres[((size_t)t * nbox + b) * 2], oy = centres[((size_t)t * nbox + b) * 2 + 1], sz = cf.obstacle_size;
-            const double raw[8] = {ox + sz, oy + sz, ox - sz, oy + sz, ox - sz, oy - sz, ox + sz, oy - sz}; // maze_NAMO_env.py:317-320
-            Shape s;
-            if (!build_floe(raw, 4, ox, oy, cf.density, cf.poly_radius, s)) continue;
-            s.radius = cf.poly_radius; s.e = cf.elasticity; s.u = cf.friction;
-            s.kind = kind_of(2, 0, BODY_DYNAMIC);
-            bodies.push_back(s);
-        }
-        for (int w = 0; w < nwalls; w++) {
-            Shape s;
-            build_wall(walls[4 * w], walls[4 * w + 1], walls[4 * w + 2], walls[4 * w + 3], s);
-            s.radius = cf.wall_radius; s.e = 0.5; s.u = 0.5;            // sim_utils.py:177-180
-            s.kind = kind_of(3, 0, BODY_STATIC);
-            bodies.push_back(s);
-        }
-    }
-    // static maps: wall raster + BFS goal map
-    std::vector<unsigned char> wall;
-    std::vector<double> norm;
-    maze_maps(walls, nwalls, cf.wall_radius, cf.map_w, cf.map_h, h->P.grid_h, h->P.grid_w, cf.goal_x, cf.goal_y, wall, norm, h->goal_raw);
+    bpgeom::MazeScene sc;
+    if (const char *e = bpgeom::maze_scene(h->cfg, h->P.grid_h, h->P.grid_w, T, nbox, centres, nwalls, walls, start, sc)) return fail(h, BP_EINVAL, e);
     int rc;
-    DevTable maps[2] = {dev_table(norm), dev_table(wall)};
+    DevTable maps[2] = {dev_table(sc.norm), dev_table(sc.wall)};
     if ((rc = upload_tables(h, maps, 2))) return rc;
     h->D.dist_map = (const double *)maps[0].dev; h->D.wall_map = (const unsigned char *)maps[1].dev;
-    {   // the observer's packed copy: sign = wall, magnitude = normalised distance (a wall cell's distance is exactly 1.0, never a zero)
-        std::vector<double> packed(norm.size());
-        for (size_t i = 0; i < norm.size(); i++) packed[i] = wall[i] ? -norm[i] : norm[i];
-        DevTable pk = dev_table(packed);
-        if ((rc = upload_tables(h, &pk, 1))) return rc;
-        h->D.maze_obs_map = (const double *)pk.dev;
-    }
-    DevTable raw = dev_table(h->goal_raw);
+    DevTable pk = dev_table(sc.obs_map);
+    if ((rc = upload_tables(h, &pk, 1))) return rc;
+    h->D.maze_obs_map = (const double *)pk.dev;
+    DevTable raw = dev_table(sc.raw);
     if ((rc = upload_tables(h, &raw, 1))) return rc;
     h->D.goal_raw = (const double *)raw.dev;
-    h->scen_hash = bp_fnv1a(wall.data(), wall.size(), h->scen_hash);
-    h->scen_hash = bp_fnv1a(norm.data(), sizeof(double) * norm.size(), h->scen_hash);
-    h->scen_hash = bp_fnv1a(h->goal_raw.data(), sizeof(double) * h->goal_raw.size(), h->scen_hash);
-    const int rc_up = upload_trials(h, trials);
+    h->goal_raw = sc.raw;
+    h->scen_hash = bpgeom::maze_scene_hash(sc, h->scen_hash);
+    const int rc_up = upload_trials(h, sc.trials);
     return rc_up ? rc_up : state_setup(h);
 }
 
@@ -1978,102 +1871,14 @@ int bp_bd_create(const bp_bd_config *cfg, int32_t num_envs, int64_t env_id_offse
     return BP_OK;
 }
 
-int bp_bd_load(bp_handle *h, int32_t T, int32_t nbox, const double *starts, const double *boxes, int32_t ns, const double *sverts,
-               const int32_t *scount, const double *spose, const double *srad, const int32_t *stype)
+// ---- the box-delivery / area-clearing loader behind upload_trials(), as a sequence of steps -----------------------------------------------------------
+// (NW: cells of the small-map window, words: its bitmap words)
+// Step 1: the static maps of every distinct layout, the receptacle polygons and the robot channel to the device; their part of the scenario hash
+static int bd_upload_maps(bp_handle *h, const bpgeom::BdScene &sc, int NW, int words)
 {
-    if (!h || T <= 0 || nbox <= 0 || nbox > BD_MAXBOX || ns <= 0 || !starts || !boxes || !sverts || !scount || !spose || !srad || !stype) return BP_EINVAL;
-    if (h->loaded) return fail(h, BP_ESTATE, "scenarios already loaded");
-    if (h->P.env_kind != BP_ENV_BOX) return fail(h, BP_ESTATE, "handle was created for another environment");
-    BP_DEVICE(h);
-    using namespace bpgeom;
-    const bp_bd_config &cf = h->bdcfg;
-    std::vector<std::vector<Shape>> trials(T);
-    std::vector<Shape> recepts(T);
-    h->bd_map_of_trial.assign(T, 0);
-    std::vector<std::vector<std::vector<P2>>> map_keys; // obstacle polygons of each distinct layout
-    for (int t = 0; t < T; t++) {
-        std::vector<Shape> &bodies = trials[t];
-        const double sx = starts[3 * t], sy = starts[3 * t + 1], sh = starts[3 * t + 2];
-        {   // create_agent (sim_utils.py:20-73): main shape radius 0 / friction 1, wheels + bumper radius 0.02 / friction 0
-            Shape s;
-            build_agent_main(cf.robot_verts, 4, sx, sy, sh, s);
-            s.radius = 0.0; s.e = 0.01; s.u = 1.0; s.kind = kind_of(1, 1, BODY_KINEMATIC);
-            bodies.push_back(s);
-            for (int k = 0; k < 5; k++) {
-                Shape w;
-                build_kinematic_part(k < 4 ? cf.wheel_verts[k] : cf.bumper_verts, 4, sx, sy, sh, w);
-                w.radius = 0.02; w.e = 0.01; w.u = 0.0; w.kind = kind_of(0, 1, BODY_KINEMATIC);
-                bodies.push_back(w);
-            }
-        }
-        for (int b = 0; b < nbox; b++) {
-            const double *bx = boxes + ((size_t)t * nbox + b) * 3;
-            Shape s;
-            if (!build_box(bx[0], bx[1], bx[2], cf.box_half, cf.box_density, 0.02, s)) return fail(h, BP_EINVAL, "degenerate box");
-            s.radius = 0.02; s.e = 0.01; s.u = 1.0; s.kind = kind_of(2, 0, BODY_DYNAMIC);
-            bodies.push_back(s);
-        }
-        std::vector<std::vector<P2>> obstacles;
-        int nrec = 0;
-        for (int k = 0; k < ns; k++) {
-            const size_t o = (size_t)t * ns + k;
-            const int n = scount[o];
-            if (n == 0) continue;   // padding: trials may hold different numbers of columns
-            if (n < 3 || n > 4) return fail(h, BP_EINVAL, "static polygons have 3 or 4 vertices");
-            Shape s;
-            build_static_poly(sverts + o * 8, n, spose[o * 3], spose[o * 3 + 1], spose[o * 3 + 2], s);
-            s.radius = srad[o]; s.e = 0.01; s.u = 1.0;
-            if (cf.task == 1) { s.e = 0.0; s.u = 0.99; }   // area_clearing.py:446-474: pymunk default elasticity, friction 0.99
-            if (stype[o] == 4) {
-                if (s.verts.size() != 4) return fail(h, BP_EINVAL, "the receptacle must be a quadrilateral");
-                recepts[t] = s; nrec++;
-                continue;            // the receptacle never produces a collision response (handlers :216-229): not a physics slot
-            }
-            s.kind = kind_of(3, 0, BODY_STATIC);
-            bodies.push_back(s);
-            obstacles.push_back(world_verts(s));
-        }
-        if (cf.task == 0 && nrec != 1) return fail(h, BP_EINVAL, "exactly one receptacle polygon per trial is required");
-        if (cf.task == 1 && nrec != 0) return fail(h, BP_EINVAL, "area-clearing has no receptacle polygon");
-        int mi = -1;
-        for (size_t m = 0; m < map_keys.size() && mi < 0; m++) {
-            bool same = map_keys[m].size() == obstacles.size();
-            for (size_t q = 0; same && q < obstacles.size(); q++) {
-                same = map_keys[m][q].size() == obstacles[q].size();
-                for (size_t v = 0; same && v < obstacles[q].size(); v++) same = map_keys[m][q][v].x == obstacles[q][v].x && map_keys[m][q][v].y == obstacles[q][v].y;
-            }
-            if (same) mi = (int)m;
-        }
-        if (mi < 0) {
-            BdMaps M;
-            AcGeom G;
-            G.nbd = cf.num_boundary_verts; G.nob = cf.num_outer_verts; G.ngoal = cf.num_goal_points;
-            G.bd = cf.boundary; G.ob = cf.outer_boundary; G.goals = cf.goal_points; G.scale_max = cf.distance_scale_max;
-            if (!bd_build_maps(obstacles, cf.room_length, cf.room_width, cf.ppm, cf.local_px, cf.local_w, cf.robot_radius, cf.robot_half_width,
-                               cf.recept_x, cf.recept_y, cf.sp_channel_scale, M, cf.task, &G, cf.task == 0 && cf.invert_receptacle_map != 0))
-                return fail(h, BP_EINVAL, "free space does not fit the small-map window");
-            h->bd_maps.push_back(M);
-            map_keys.push_back(obstacles);
-            mi = (int)map_keys.size() - 1;
-        }
-        h->bd_map_of_trial[t] = mi;
-    }
-    int rc = upload_trials(h, trials, false);
-    if (rc) return rc;
-    if (h->nbcap > 64) return fail(h, BP_EINVAL, "box-delivery supports at most 64 shape slots per env");
-    BdParams &B = h->B;
-    const BdMaps &M0 = h->bd_maps[0];
-    B.H = M0.H; B.W = M0.W; B.SH = M0.SH; B.SW = M0.SW; B.si0 = M0.si0; B.sj0 = M0.sj0;
-    B.nbox = nbox; B.nrecept = 1; B.out_r = M0.out_r;
-    B.budget = 0; B.pass = 0; B.sel_want = -1; B.resume_sel = 0;
-    // execute_robot_path skips whole periods once the robot's state recurs exactly (a robot that pushes against a wall until STEP_LIMIT); BP_BD_CYCLE=0: every sim step is run
-    // (in the second pass of the two-pass step, whose envs are already beyond the first pass's budget: from the first sim step of the pass on; BP_BD_CYCLE=<n>: only
-    //  once a path has run n sim steps)
-    B.cycle_skip = getenv("BP_BD_CYCLE") ? std::max(0, atoi(getenv("BP_BD_CYCLE"))) : 1;
-    // two-pass step: sim steps every env gets in pass 0 (the mean env needs ~750, the 99th percentile ~3 000; the reference's loops stop at 10 001); BP_BD_BUDGET=0: one pass
-    h->bd_budget = getenv("BP_BD_BUDGET") ? atoi(getenv("BP_BD_BUDGET")) : 3000;
-    const int NW = B.SH * B.SW, words = (NW + 31) / 32, nm = (int)h->bd_maps.size();
-    BdPtrs &Q = h->Q;
+    const int T = (int)sc.map_of_trial.size(), nm = (int)sc.maps.size();
+    const bool recept = h->bdcfg.task == 0;
+    int rc;
     int *d_mot; unsigned *d_free, *d_thin; unsigned short *d_edt; float *d_rec; unsigned char *d_small, *d_rchan; d2 *d_rp, *d_rn;
     if ((rc = dalloc(h, &d_mot, T))) return rc;
     if ((rc = dalloc(h, &d_free, (size_t)nm * words))) return rc;
@@ -2083,48 +1888,33 @@ int bp_bd_load(bp_handle *h, int32_t T, int32_t nbox, const double *starts, cons
     if ((rc = dalloc(h, &d_small, (size_t)nm * NW))) return rc;
     if ((rc = dalloc(h, &d_rp, (size_t)nm * 4))) return rc;
     if ((rc = dalloc(h, &d_rn, (size_t)nm * 4))) return rc;
-    if ((rc = dalloc(h, &d_rchan, (size_t)B.local_px * B.local_px))) return rc;
-    HIPCHK(h, hipMemcpy(d_mot, h->bd_map_of_trial.data(), sizeof(int) * T, hipMemcpyHostToDevice));
-    h->scen_hash = bp_fnv1a(h->bd_map_of_trial.data(), sizeof(int) * T, h->scen_hash);
-    std::vector<int> first_trial_of_map(nm, -1);
-    for (int t = 0; t < T; t++) if (first_trial_of_map[h->bd_map_of_trial[t]] < 0) first_trial_of_map[h->bd_map_of_trial[t]] = t;
+    if ((rc = dalloc(h, &d_rchan, sc.robot_chan.size()))) return rc;
+    HIPCHK(h, hipMemcpy(d_mot, sc.map_of_trial.data(), sizeof(int) * T, hipMemcpyHostToDevice));
     for (int m = 0; m < nm; m++) {
-        const BdMaps &M = h->bd_maps[m];
+        const bpgeom::BdMaps &M = sc.maps[m];
         HIPCHK(h, hipMemcpy(d_free + (size_t)m * words, M.free_bits.data(), sizeof(unsigned) * words, hipMemcpyHostToDevice));
         HIPCHK(h, hipMemcpy(d_thin + (size_t)m * words, M.thin_bits.data(), sizeof(unsigned) * words, hipMemcpyHostToDevice));
         HIPCHK(h, hipMemcpy(d_edt + (size_t)m * NW * 2, M.edt.data(), sizeof(unsigned short) * NW * 2, hipMemcpyHostToDevice));
         HIPCHK(h, hipMemcpy(d_rec + (size_t)m * NW, M.recept.data(), sizeof(float) * NW, hipMemcpyHostToDevice));
         HIPCHK(h, hipMemcpy(d_small + (size_t)m * NW, M.small_free.data(), NW, hipMemcpyHostToDevice));
-        h->scen_hash = bp_fnv1a(M.free_bits.data(), sizeof(unsigned) * words, h->scen_hash);
-        h->scen_hash = bp_fnv1a(M.thin_bits.data(), sizeof(unsigned) * words, h->scen_hash);
-        h->scen_hash = bp_fnv1a(M.edt.data(), sizeof(unsigned short) * NW * 2, h->scen_hash);
-        h->scen_hash = bp_fnv1a(M.recept.data(), sizeof(float) * NW, h->scen_hash);
-        h->scen_hash = bp_fnv1a(M.small_free.data(), NW, h->scen_hash);
-        if (cf.task == 0) {
-            const Shape &r = recepts[first_trial_of_map[m]];
-            const std::vector<P2> wv = world_verts(r);
-            d2 hp[4], hn[4];
-            for (int i = 0; i < 4; i++) { hp[i].x = wv[i].x; hp[i].y = wv[i].y; hn[i].x = r.normals[i].x; hn[i].y = r.normals[i].y; }
-            HIPCHK(h, hipMemcpy(d_rp + (size_t)m * 4, hp, sizeof(hp), hipMemcpyHostToDevice));
-            HIPCHK(h, hipMemcpy(d_rn + (size_t)m * 4, hn, sizeof(hn), hipMemcpyHostToDevice));
-            h->scen_hash = bp_fnv1a(hp, sizeof(hp), h->scen_hash);
+        if (recept) {
+            HIPCHK(h, hipMemcpy(d_rp + (size_t)m * 4, &sc.recept_poly[4 * (size_t)m], sizeof(d2) * 4, hipMemcpyHostToDevice));
+            HIPCHK(h, hipMemcpy(d_rn + (size_t)m * 4, &sc.recept_n[4 * (size_t)m], sizeof(d2) * 4, hipMemcpyHostToDevice));
         }
     }
-    {   // robot_state_channel (box_delivery_env.py:124-131) * 255
-        const int lp = B.local_px;
-        std::vector<unsigned char> rc_((size_t)lp * lp, 0);
-        const int rpw = (int)(2 * cf.robot_radius * cf.ppm);
-        const int start = (int)std::floor((double)lp / 2 - (double)rpw / 2);
-        for (int i = start; i < start + rpw; i++)
-            for (int j = start; j < start + rpw; j++) {
-                if (i < 0 || j < 0 || i >= lp || j >= lp) continue;
-                const double a = ((double)i + 0.5) - (double)lp / 2, b = ((double)j + 0.5) - (double)lp / 2;
-                if (std::sqrt(a * a + b * b) < (double)rpw / 2) rc_[(size_t)i * lp + j] = 255;
-            }
-        HIPCHK(h, hipMemcpy(d_rchan, rc_.data(), rc_.size(), hipMemcpyHostToDevice));
-    }
+    HIPCHK(h, hipMemcpy(d_rchan, sc.robot_chan.data(), sc.robot_chan.size(), hipMemcpyHostToDevice));
+    BdPtrs &Q = h->Q;
     Q.map_of_trial = d_mot; Q.free_bits = d_free; Q.thin_bits = d_thin; Q.edt = d_edt; Q.recept = d_rec; Q.small_free = d_small;
     Q.recept_poly = d_rp; Q.recept_n = d_rn; Q.robot_chan = d_rchan;
+    h->scen_hash = bpgeom::bd_scene_hash(sc, h->scen_hash);
+    return BP_OK;
+}
+// Step 2: the task state of the E envs plus T templates, next to alloc_env_state's
+static int bd_alloc_env_state(bp_handle *h, int T, int NW)
+{
+    const bp_bd_config &cf = h->bdcfg;
+    BdPtrs &Q = h->Q;
+    int rc;
     const size_t E = (size_t)h->num_envs + (size_t)T;
     if ((rc = dalloc(h, &Q.alive, E * BD_MAXBOX))) return rc;
     if ((rc = dalloc(h, &Q.order, E * BD_MAXBOX))) return rc;
@@ -2146,41 +1936,74 @@ int bp_bd_load(bp_handle *h, int32_t T, int32_t nbox, const double *starts, cons
     if ((rc = dalloc(h, &Q.rmap, E * NW))) return rc;
     if ((rc = dalloc(h, &Q.cleared, E * BD_MAXBOX))) return rc;
     if ((rc = dalloc(h, &Q.m_box, E * BD_MAXBOX * 3))) return rc;
-    {
-        d2 *d_goals;
-        if ((rc = dalloc(h, &d_goals, 128))) return rc;
-        if (cf.task == 1) HIPCHK(h, hipMemcpy(d_goals, cf.goal_points, sizeof(d2) * (size_t)cf.num_goal_points, hipMemcpyHostToDevice));
-        Q.goals = d_goals;
-    }
+    d2 *d_goals;
+    if ((rc = dalloc(h, &d_goals, 128))) return rc;
+    if (cf.task == 1) HIPCHK(h, hipMemcpy(d_goals, cf.goal_points, sizeof(d2) * (size_t)cf.num_goal_points, hipMemcpyHostToDevice));
+    Q.goals = d_goals;
+    return BP_OK;
+}
+// Step 3: the dynamic-LDS size of each kernel family, and the limit of every kernel that may be launched with it
+static int bd_lds_limits(bp_handle *h, int NW, int words)
+{
     h->bd_lds = (size_t)words * 8 + (size_t)3 * BD_QCAP * 2 + 16 + (size_t)BD_PATHCAP * 2 * 2 + BD_PATHCAP + (size_t)BD_PATHCAP * 4 + (size_t)BD_MAXWP * 16 + 64;
     h->bd_obs_lds = (size_t)((NW + 15) & ~15);
+    h->bd_rmap_lds = (((size_t)words + 3) & ~(size_t)3) * 4 + (size_t)3 * BD_QCAP * 2 + 16;
     if (h->bd_lds > 160 * 1024 || h->bd_obs_lds > 160 * 1024) return fail(h, BP_EINVAL, "map window too large for LDS");
-    HIPCHK(h, hipFuncSetAttribute((const void *)k_bd_settle, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
-    HIPCHK(h, hipFuncSetAttribute((const void *)k_bd_physics, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
-    HIPCHK(h, hipFuncSetAttribute((const void *)k_bd_physics_resume, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
-    HIPCHK(h, hipFuncSetAttribute((const void *)k_bd_physics_damp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
-    HIPCHK(h, hipFuncSetAttribute((const void *)k_bd_slice, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
-    HIPCHK(h, hipFuncSetAttribute((const void *)k_bd_slice_resume, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
-    HIPCHK(h, hipFuncSetAttribute((const void *)k_bd_settle_damp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
     h->damp = h->P.damping_pow != 0.0;   // space.damping != 0: the generic instantiations (substep<BP_ENV_BOX, DAMP = true>)
-    HIPCHK(h, hipFuncSetAttribute((const void *)k_bd_plan, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->bd_lds));
-    HIPCHK(h, hipFuncSetAttribute((const void *)k_bd_plan_async, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->bd_lds));
-    HIPCHK(h, hipFuncSetAttribute((const void *)k_bd_finish, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->bd_lds));
-    HIPCHK(h, hipFuncSetAttribute((const void *)k_ac_finish, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->bd_lds));
-    HIPCHK(h, hipFuncSetAttribute((const void *)k_bd_observe, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->bd_obs_lds));
-    {
-        const size_t words = (size_t)((h->B.SH * h->B.SW + 31) / 32);
-        h->bd_rmap_lds = ((words + 3) & ~(size_t)3) * 4 + (size_t)3 * BD_QCAP * 2 + 16;
-        HIPCHK(h, hipFuncSetAttribute((const void *)k_bd_robot_map, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->bd_rmap_lds));
-    }
-    // settle every trial once into its template slot, then the episode-start bookkeeping (box distances, robot map)
+    const struct { const void *kernel; size_t bytes; } limits[] = {
+        {(const void *)k_bd_settle, h->lds_bytes},        {(const void *)k_bd_physics, h->lds_bytes},      {(const void *)k_bd_physics_resume, h->lds_bytes},
+        {(const void *)k_bd_physics_damp, h->lds_bytes},  {(const void *)k_bd_slice, h->lds_bytes},        {(const void *)k_bd_slice_resume, h->lds_bytes},
+        {(const void *)k_bd_settle_damp, h->lds_bytes},   {(const void *)k_bd_plan, h->bd_lds},            {(const void *)k_bd_plan_async, h->bd_lds},
+        {(const void *)k_bd_finish, h->bd_lds},           {(const void *)k_ac_finish, h->bd_lds},          {(const void *)k_bd_observe, h->bd_obs_lds},
+        {(const void *)k_bd_robot_map, h->bd_rmap_lds},
+    };
+    for (const auto &l : limits) HIPCHK(h, hipFuncSetAttribute(l.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.bytes));
+    return BP_OK;
+}
+// Step 4: settle every trial once into its template slot, then the episode-start bookkeeping (box distances, robot map)
+static int bd_settle_templates(bp_handle *h)
+{
+    const int T = h->num_trials;
     if (h->damp) hipLaunchKernelGGL(k_bd_settle_damp, dim3(T), dim3(64), h->lds_bytes, 0, h->P, h->D, (const unsigned char *)nullptr, (double *)nullptr, 1);
     else hipLaunchKernelGGL(k_bd_settle, dim3(T), dim3(64), h->lds_bytes, 0, h->P, h->D, (const unsigned char *)nullptr, (double *)nullptr, 1);
     HIPCHK(h, hipGetLastError());
-    if ((rc = bd_finish(h, h->B, 0, StepOut{}, 1))) return rc;
+    if (int rc = bd_finish(h, h->B, 0, StepOut{}, 1)) return rc;
     hipLaunchKernelGGL(k_bd_robot_map, dim3(T), dim3(BDR_THREADS), h->bd_rmap_lds, 0, h->P, h->D, h->B, h->Q, 1);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipDeviceSynchronize());
+    return BP_OK;
+}
+
+int bp_bd_load(bp_handle *h, int32_t T, int32_t nbox, const double *starts, const double *boxes, int32_t ns, const double *sverts,
+               const int32_t *scount, const double *spose, const double *srad, const int32_t *stype)
+{
+    if (!h || T <= 0 || nbox <= 0 || nbox > BD_MAXBOX || ns <= 0 || !starts || !boxes || !sverts || !scount || !spose || !srad || !stype) return BP_EINVAL;
+    if (h->loaded) return fail(h, BP_ESTATE, "scenarios already loaded");
+    if (h->P.env_kind != BP_ENV_BOX) return fail(h, BP_ESTATE, "handle was created for another environment");
+    BP_DEVICE(h);
+    bpgeom::BdScene sc;
+    if (const char *e = bpgeom::bd_scene(h->bdcfg, T, nbox, starts, boxes, ns, sverts, scount, spose, srad, stype, sc)) return fail(h, BP_EINVAL, e);
+    h->bd_maps = sc.maps;   // (bp_bd_get_maps) only now: a refused load leaves the handle as bp_bd_create made it
+    h->bd_map_of_trial = sc.map_of_trial;
+    int rc = upload_trials(h, sc.trials, false);
+    if (rc) return rc;
+    if (h->nbcap > 64) return fail(h, BP_EINVAL, "box-delivery supports at most 64 shape slots per env");
+    BdParams &B = h->B;
+    const bpgeom::BdMaps &M0 = sc.maps[0];
+    B.H = M0.H; B.W = M0.W; B.SH = M0.SH; B.SW = M0.SW; B.si0 = M0.si0; B.sj0 = M0.sj0;
+    B.nbox = nbox; B.nrecept = 1; B.out_r = M0.out_r;
+    B.budget = 0; B.pass = 0; B.sel_want = -1; B.resume_sel = 0;
+    // execute_robot_path skips whole periods once the robot's state recurs exactly (a robot that pushes against a wall until STEP_LIMIT); BP_BD_CYCLE=0: every sim step is run
+    // (in the second pass of the two-pass step, whose envs are already beyond the first pass's budget: from the first sim step of the pass on; BP_BD_CYCLE=<n>: only
+    //  once a path has run n sim steps)
+    B.cycle_skip = getenv("BP_BD_CYCLE") ? std::max(0, atoi(getenv("BP_BD_CYCLE"))) : 1;
+    // two-pass step: sim steps every env gets in pass 0 (the mean env needs ~750, the 99th percentile ~3 000; the reference's loops stop at 10 001); BP_BD_BUDGET=0: one pass
+    h->bd_budget = getenv("BP_BD_BUDGET") ? atoi(getenv("BP_BD_BUDGET")) : 3000;
+    const int NW = B.SH * B.SW, words = (NW + 31) / 32;
+    if ((rc = bd_upload_maps(h, sc, NW, words))) return rc;
+    if ((rc = bd_alloc_env_state(h, T, NW))) return rc;
+    if ((rc = bd_lds_limits(h, NW, words))) return rc;
+    if ((rc = bd_settle_templates(h))) return rc;
     if ((rc = state_setup(h))) return rc;
     h->loaded = true;
     return BP_OK;

@@ -5,13 +5,13 @@
 #include <stdint.h>
 
 #include "../../include/benchpush_amd.h"
+#include "bp_host_geom.hpp"   // BODY_*, kind_of, bp_fnv1a: shared with the host-only scene builders
 
 #define BP_KADJ 24   // Verlet neighbour slots per body
 #define BP_ACAP 64   // arbiter (contact pair) slots per env: one per lane
 
 typedef double2 d2;
 
-enum { BODY_DYNAMIC = 0, BODY_KINEMATIC = 1, BODY_STATIC = 2 };
 __device__ __forceinline__ int kind_ctype(int k) { return k & 0xFF; }
 __device__ __forceinline__ int kind_group(int k) { return (k >> 8) & 0xFF; }
 __device__ __forceinline__ int kind_btype(int k) { return (k >> 16) & 3; }

@@ -10,8 +10,22 @@
 #pragma once
 #include <cmath>
 #include <cfloat>
+#include <cstddef>
 #include <utility>
 #include <vector>
+
+// Shape::kind, as the loaders write it and the kernels read it (bp_device.hpp: kind_ctype / kind_group / kind_btype)
+enum { BODY_DYNAMIC = 0, BODY_KINEMATIC = 1, BODY_STATIC = 2 };
+static inline int kind_of(int ctype, int group, int btype) { return ctype | (group << 8) | (btype << 16); }
+
+// FNV-1a, the hash of the state records' layout id (bp_state.hpp) and of the scenario tables that go into it (bp_host_scene.hpp)
+inline unsigned long long bp_fnv1a(const void *data, size_t n, unsigned long long h = 0xCBF29CE484222325ull)
+{
+    const unsigned char *p = (const unsigned char *)data;
+    for (size_t i = 0; i < n; i++) { h ^= p[i]; h *= 0x100000001B3ull; }
+    return h;
+}
+inline unsigned long long bp_fnv1a_i64(long long v, unsigned long long h) { return bp_fnv1a(&v, sizeof(v), h); }
 
 namespace bpgeom {
 

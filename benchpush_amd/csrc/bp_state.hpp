@@ -34,14 +34,6 @@ struct BpStateLayout {
     const char *name[BP_STATE_MAXSEG];
 };
 
-inline unsigned long long bp_fnv1a(const void *data, size_t n, unsigned long long h = 0xCBF29CE484222325ull)
-{
-    const unsigned char *p = (const unsigned char *)data;
-    for (size_t i = 0; i < n; i++) { h ^= p[i]; h *= 0x100000001B3ull; }
-    return h;
-}
-inline unsigned long long bp_fnv1a_i64(long long v, unsigned long long h) { return bp_fnv1a(&v, sizeof(v), h); }
-
 inline void bp_state_add(BpStateLayout &L, const char *name, const void *base, unsigned long long span, unsigned kind = BP_SEG_COPY)
 {
     if (L.nseg >= BP_STATE_MAXSEG) return;   // (static table below: 50 rows at most; bp_state_layout's callers check nseg)

@@ -65,11 +65,17 @@ class BatchedBoxDeliveryEnv(BatchedShipIceEnv):
             trials = self._generate_trials(self.cfg, num_trials, seed)
         self.trials = trials
         self.nbox = nbox = len(trials[0]["boxes"])
-        ns = max(len(t["statics"][1]) for t in trials)
         if self._same_box_count and any(len(t["boxes"]) != nbox for t in trials):
             raise ValueError("all trials must hold the same number of boxes")
         self.bd_params["num_boxes"] = nbox
         self._create(self.L.bp_bd_create, self._bd_config())
+        self._load(trials)
+
+    def _load(self, trials):
+        """bp_bd_load with its arguments packed from the trial dicts, then the output tensors.  A refused load (BpError) leaves the handle as it was created,
+        so it may be called again with other trials of the same box count."""
+        self.trials, nbox = trials, self.nbox
+        ns = max(len(t["statics"][1]) for t in trials)
         c = lambda a, dt: np.ascontiguousarray(a, dt)
         starts = c(np.stack([t["start"] for t in trials]), np.float64)
         boxes = c(np.stack([t["boxes"] for t in trials]), np.float64)

@@ -1,10 +1,16 @@
-// CPU sanitizer harness for the HOST-side product code: benchpush_amd/csrc/bp_host_geom.hpp + bp_host_bd.hpp -- hulls, mass
-// properties, fillPoly, disk dilation, EDT indices, spfa, maze maps -- are normally compiled only inside the .hip translation unit, where no sanitizer
-// runs (GPU ASan is not available on the pool).  This program includes the same two headers, is built with -fsanitize=address,undefined by
-// tests/test_host_sanitize.py, and replays the load-time sequences of bp_load_scenarios / bp_load_maze / bp_bd_load (bp_capi.hip) on case files that the
-// test writes from the shipped configurations: the arguments are exactly the arrays the Python envs hand to those entry points.
+// CPU sanitizer harness for the HOST-side product code.  The host halves of the three loaders -- bp_host_scene.hpp: the scene
+// builders of bp_load_scenarios / bp_load_maze / bp_bd_load and pack_trials, over bp_host_geom.hpp + bp_host_bd.hpp: hulls, mass properties, fillPoly,
+// disk dilation, EDT indices, spfa, maze maps -- are plain C++ that bp_capi.hip calls before its first HIP call.  Inside the .hip translation unit no
+// sanitizer runs (GPU ASan is not available on the pool), so this program includes the same headers, is built with -fsanitize=address,undefined by
+// tests/test_host_sanitize.py, and calls the same builders on case files that the test writes: the arguments are exactly the arrays the Python envs hand
+// to those entry points.  Nothing of the loaders is restated here.
 //
-//   host_sanitize <case-file>      prints one line per record and "host-sanitize-ok <records>" at the end; exit code 0 unless a loader refused a case
+//   host_sanitize <case-file>            one line per record and "host-sanitize-ok <records>" at the end; exit code 0 unless a builder refused a record
+//   host_sanitize --refuse <case-file>   every record must be refused: prints "refused: <the builder's message>" per record and
+//                                        "host-sanitize-refused <records>"; exit code 0 only if no record was accepted
+//
+// A record's line: counts, `checksum` over mass, pose, hull vertices and planes of every body, `materials` over radius, elasticity, friction and kind, and
+// the scenario hash that the library folds into the state records' layout id.
 //
 // File format (little endian): records of  int32 tag ; payload
 //   tag 1 ship-ice : bp_config ; int32 T, F, V ; double verts[T][F][V][2] ; int32 counts[T][F] ; double centres[T][F][2] ; double starts[T][3] ; int32 nfloes[T]
@@ -16,8 +22,7 @@
 #include <cstring>
 #include <vector>
 
-#include "../../include/benchpush_amd.h"
-#include "../../benchpush_amd/csrc/bp_host_bd.hpp"
+#include "../../benchpush_amd/csrc/bp_host_scene.hpp"
 
 using namespace bpgeom;
 
@@ -30,7 +35,9 @@ template <typename T> static std::vector<T> rd(size_t n)
 }
 template <typename T> static T rd1() { return rd<T>(1)[0]; }
 
-static double checksum(const std::vector<std::vector<Shape>> &trials)
+static const unsigned long long HASH0 = 0xCBF29CE484222325ull;   // bp_handle::scen_hash of a fresh handle
+
+static double checksum(const Trials &trials)
 {
     double s = 0.0;
     for (const auto &b : trials)
@@ -41,8 +48,27 @@ static double checksum(const std::vector<std::vector<Shape>> &trials)
         }
     return s;
 }
+static double materials(const Trials &trials)
+{
+    double s = 0.0;
+    for (const auto &b : trials)
+        for (const Shape &sh : b) s += sh.radius + sh.e + sh.u + (double)sh.kind;
+    return s;
+}
+static size_t bodies(const Trials &trials)
+{
+    size_t nb = 0;
+    for (const auto &b : trials) nb += b.size();
+    return nb;
+}
+static const char *pack(const Trials &trials, unsigned long long &hash)
+{
+    TrialTables tt;
+    return pack_trials(trials, trials_nbcap(trials), tt, hash);
+}
 
-static int ship_ice()
+// Each record: read it, call the builder and the packing, print the line.  Returns the refusal message, or nullptr.
+static const char *ship_ice()
 {
     const bp_config cf = rd1<bp_config>();
     const int T = rd1<int32_t>(), F = rd1<int32_t>(), V = rd1<int32_t>();
@@ -51,71 +77,38 @@ static int ship_ice()
     const auto centres = rd<double>((size_t)T * F * 2);
     const auto starts = rd<double>((size_t)T * 3);
     const auto nfloes = rd<int32_t>(T);
-    std::vector<std::vector<Shape>> trials(T);
-    size_t nb = 0;
-    for (int t = 0; t < T; t++) {                       // bp_load_scenarios
-        Shape ship;
-        build_ship(cf.ship_verts, cf.num_ship_verts, starts[3 * t], starts[3 * t + 1], starts[3 * t + 2], ship);
-        trials[t].push_back(ship);
-        if (nfloes[t] > F) return 1;
-        for (int f = 0; f < nfloes[t]; f++) {
-            const int n = counts[(size_t)t * F + f];
-            if (n < 3) continue;
-            if (n > V) return 1;
-            Shape s;
-            if (!build_floe(verts.data() + ((size_t)t * F + f) * V * 2, n, centres[((size_t)t * F + f) * 2], centres[((size_t)t * F + f) * 2 + 1], cf.density,
-                            cf.poly_radius, s))
-                continue;
-            if ((int)s.verts.size() > BP_MAXV) return 1;
-            trials[t].push_back(s);
-        }
-        nb += trials[t].size();
-    }
-    printf("ship-ice: %d trials, %zu bodies, checksum %.17g\n", T, nb, checksum(trials));
-    return 0;
+    Trials trials;
+    unsigned long long hash = HASH0;
+    if (const char *e = ship_ice_scene(cf, T, F, V, verts.data(), counts.data(), centres.data(), starts.data(), nfloes.data(), trials)) return e;
+    if (const char *e = pack(trials, hash)) return e;
+    printf("ship-ice: %d trials, %zu bodies, checksum %.17g, materials %.17g, scenario hash %016llx\n", T, bodies(trials), checksum(trials), materials(trials), hash);
+    return nullptr;
 }
 
-static int maze()
+static const char *maze()
 {
     const bp_config cf = rd1<bp_config>();
     const int T = rd1<int32_t>(), nbox = rd1<int32_t>(), nwalls = rd1<int32_t>(), gh = rd1<int32_t>(), gw = rd1<int32_t>();
     const auto centres = rd<double>((size_t)T * nbox * 2);
     const auto walls = rd<double>((size_t)nwalls * 4);
     const auto start = rd<double>((size_t)T * 3);
-    std::vector<std::vector<Shape>> trials(T);
-    for (int t = 0; t < T; t++) {                       // bp_load_maze
-        for (int k = 0; k <= cf.num_wheels; k++) {
-            Shape s;
-            const double *st3 = start.data() + 3 * (size_t)t;
-            if (k == 0) build_kinematic_part(cf.ship_verts, cf.num_ship_verts, st3[0], st3[1], st3[2], s);
-            else build_kinematic_part(cf.wheel_verts[k - 1], 4, st3[0], st3[1], st3[2], s);
-            trials[t].push_back(s);
-        }
-        for (int b = 0; b < nbox; b++) {
-            const double ox = centres[((size_t)t * nbox + b) * 2], oy = centres[((size_t)t * nbox + b) * 2 + 1], sz = cf.obstacle_size;
-            const double raw[8] = {ox + sz, oy + sz, ox - sz, oy + sz, ox - sz, oy - sz, ox + sz, oy - sz};
-            Shape s;
-            if (!build_floe(raw, 4, ox, oy, cf.density, cf.poly_radius, s)) continue;
-            trials[t].push_back(s);
-        }
-        for (int w = 0; w < nwalls; w++) {
-            Shape s;
-            build_wall(walls[4 * w], walls[4 * w + 1], walls[4 * w + 2], walls[4 * w + 3], s);
-            trials[t].push_back(s);
-        }
-    }
-    std::vector<unsigned char> wall;
-    std::vector<double> norm, raw;
-    maze_maps(walls.data(), nwalls, cf.wall_radius, cf.map_w, cf.map_h, gh, gw, cf.goal_x, cf.goal_y, wall, norm, raw);
+    MazeScene sc;
+    if (const char *e = maze_scene(cf, gh, gw, T, nbox, centres.data(), nwalls, walls.data(), start.data(), sc)) return e;
+    unsigned long long hash = maze_scene_hash(sc, HASH0);
+    if (const char *e = pack(sc.trials, hash)) return e;
     size_t nwall = 0;
     double mx = 0.0;
-    for (size_t i = 0; i < wall.size(); i++) { nwall += wall[i]; if (raw[i] > mx) mx = raw[i]; }
-    printf("maze: %d layouts x %d boxes, %d walls, grid %dx%d: %zu wall cells, longest wavefront %.0f, checksum %.17g\n", T, nbox, nwalls, gh, gw, nwall, mx,
-           checksum(trials));
-    return 0;
+    for (size_t i = 0; i < sc.wall.size(); i++) {
+        nwall += sc.wall[i];
+        if (sc.raw[i] > mx) mx = sc.raw[i];
+        if ((sc.obs_map[i] < 0) != (sc.wall[i] != 0)) { fprintf(stderr, "observer map: sign != wall\n"); exit(4); }
+    }
+    printf("maze: %d layouts x %d boxes, %d walls, grid %dx%d: %zu wall cells, longest wavefront %.0f, checksum %.17g, materials %.17g, scenario hash %016llx\n", T,
+           nbox, nwalls, gh, gw, nwall, mx, checksum(sc.trials), materials(sc.trials), hash);
+    return nullptr;
 }
 
-static int box()
+static const char *box()
 {
     const bp_bd_config cf = rd1<bp_bd_config>();
     const int T = rd1<int32_t>(), nbox = rd1<int32_t>(), ns = rd1<int32_t>();
@@ -126,83 +119,37 @@ static int box()
     const auto spose = rd<double>((size_t)T * ns * 3);
     const auto srad = rd<double>((size_t)T * ns);
     const auto stype = rd<int32_t>((size_t)T * ns);
-    std::vector<std::vector<Shape>> trials(T);
-    std::vector<std::vector<std::vector<P2>>> map_keys;
+    BdScene sc;
+    unsigned long long hash = HASH0;
+    if (const char *e = bd_scene(cf, T, nbox, starts.data(), boxes.data(), ns, sverts.data(), scount.data(), spose.data(), srad.data(), stype.data(), sc)) return e;
+    if (const char *e = pack(sc.trials, hash)) return e;
+    hash = bd_scene_hash(sc, hash);
     size_t free_cells = 0;
-    for (int t = 0; t < T; t++) {                       // bp_bd_load
-        std::vector<Shape> &bodies = trials[t];
-        const double sx = starts[3 * t], sy = starts[3 * t + 1], sh = starts[3 * t + 2];
-        {
-            Shape s;
-            build_agent_main(cf.robot_verts, 4, sx, sy, sh, s);
-            bodies.push_back(s);
-            for (int k = 0; k < 5; k++) {
-                Shape w;
-                build_kinematic_part(k < 4 ? cf.wheel_verts[k] : cf.bumper_verts, 4, sx, sy, sh, w);
-                bodies.push_back(w);
-            }
-        }
-        for (int b = 0; b < nbox; b++) {
-            const double *bx = boxes.data() + ((size_t)t * nbox + b) * 3;
-            Shape s;
-            if (!build_box(bx[0], bx[1], bx[2], cf.box_half, cf.box_density, 0.02, s)) return 1;
-            bodies.push_back(s);
-        }
-        std::vector<std::vector<P2>> obstacles;
-        int nrec = 0;
-        for (int k = 0; k < ns; k++) {
-            const size_t o = (size_t)t * ns + k;
-            const int n = scount[o];
-            if (n == 0) continue;
-            if (n < 3 || n > 4) return 1;
-            Shape s;
-            build_static_poly(sverts.data() + o * 8, n, spose[o * 3], spose[o * 3 + 1], spose[o * 3 + 2], s);
-            s.radius = srad[o];
-            if (stype[o] == 4) { if (s.verts.size() != 4) return 1; nrec++; (void)world_verts(s); continue; }
-            bodies.push_back(s);
-            obstacles.push_back(world_verts(s));
-        }
-        if (cf.task == 0 && nrec != 1) return 1;
-        if (cf.task == 1 && nrec != 0) return 1;
-        bool seen = false;
-        for (const auto &mk : map_keys) {
-            bool same = mk.size() == obstacles.size();
-            for (size_t q = 0; same && q < obstacles.size(); q++) {
-                same = mk[q].size() == obstacles[q].size();
-                for (size_t v = 0; same && v < obstacles[q].size(); v++) same = mk[q][v].x == obstacles[q][v].x && mk[q][v].y == obstacles[q][v].y;
-            }
-            seen = seen || same;
-        }
-        if (!seen) {
-            BdMaps M;
-            AcGeom G;
-            G.nbd = cf.num_boundary_verts; G.nob = cf.num_outer_verts; G.ngoal = cf.num_goal_points;
-            G.bd = cf.boundary; G.ob = cf.outer_boundary; G.goals = cf.goal_points; G.scale_max = cf.distance_scale_max;
-            if (!bd_build_maps(obstacles, cf.room_length, cf.room_width, cf.ppm, cf.local_px, cf.local_w, cf.robot_radius, cf.robot_half_width, cf.recept_x,
-                               cf.recept_y, cf.sp_channel_scale, M, cf.task, &G, cf.task == 0 && cf.invert_receptacle_map != 0))
-                return 1;
-            for (unsigned w : M.free_bits) free_cells += (size_t)__builtin_popcount(w);
-            map_keys.push_back(obstacles);
-        }
-    }
-    printf("%s: %d trials x %d boxes, %zu distinct layouts, %zu free cells, checksum %.17g\n", cf.task == 1 ? "area-clearing" : "box-delivery", T, nbox,
-           map_keys.size(), free_cells, checksum(trials));
-    return 0;
+    for (const BdMaps &M : sc.maps)
+        for (unsigned w : M.free_bits) free_cells += (size_t)__builtin_popcount(w);
+    printf("%s: %d trials x %d boxes, %zu distinct layouts, %zu free cells, checksum %.17g, materials %.17g, scenario hash %016llx\n",
+           cf.task == 1 ? "area-clearing" : "box-delivery", T, nbox, sc.maps.size(), free_cells, checksum(sc.trials), materials(sc.trials), hash);
+    return nullptr;
 }
 
 int main(int argc, char **argv)
 {
-    if (argc != 2) { fprintf(stderr, "usage: host_sanitize <case-file>\n"); return 2; }
-    g_f = fopen(argv[1], "rb");
-    if (!g_f) { perror(argv[1]); return 2; }
-    int records = 0, rc = 0;
+    const bool refuse = argc == 3 && !strcmp(argv[1], "--refuse");
+    if (argc != 2 && !refuse) { fprintf(stderr, "usage: host_sanitize [--refuse] <case-file>\n"); return 2; }
+    g_f = fopen(argv[argc - 1], "rb");
+    if (!g_f) { perror(argv[argc - 1]); return 2; }
+    int records = 0, accepted = 0;
     int32_t tag;
     while (fread(&tag, sizeof(tag), 1, g_f) == 1) {
-        rc = tag == 1 ? ship_ice() : tag == 2 ? maze() : tag == 3 ? box() : 9;
-        if (rc) { fprintf(stderr, "record %d (tag %d) refused: rc %d\n", records, tag, rc); return 1; }
+        if (tag < 1 || tag > 3) { fprintf(stderr, "record %d: unknown tag %d\n", records, tag); return 2; }
+        const char *e = tag == 1 ? ship_ice() : tag == 2 ? maze() : box();
+        if (refuse && e) printf("refused: %s\n", e);
+        else if (e) { fprintf(stderr, "record %d (tag %d) refused: %s\n", records, tag, e); return 1; }
+        else accepted++;
         records++;
     }
     fclose(g_f);
-    printf("host-sanitize-ok %d\n", records);
+    if (refuse && accepted) { fprintf(stderr, "%d of %d records were accepted\n", accepted, records); return 1; }
+    printf(refuse ? "host-sanitize-refused %d\n" : "host-sanitize-ok %d\n", records);
     return 0;
 }
