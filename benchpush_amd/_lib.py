@@ -64,6 +64,15 @@ class BpRolloutBatch(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("obs", "action", "value", "logp", "advantage", "ret", "index", "valid")]
 
 
+class BpTransitionsDesc(C.Structure):
+    _fields_ = [("steps", C.c_int32), ("num_envs", C.c_int32), ("device", C.c_int32), ("action_dim", C.c_int32), ("row_bytes", C.c_int64)] + \
+               [(n, C.c_void_p) for n in ("obs", "next_obs", "action", "reward", "done", "timeout", "hdr")]
+
+
+class BpTransitionsBatch(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("obs", "next_obs", "action", "reward", "done", "slot", "valid")]
+
+
 class BpLatticeConfig(C.Structure):
     _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("S", C.c_int32), ("nh", C.c_int32), ("nb", C.c_int32), ("ne_max", C.c_int32), ("den", C.c_int32),
                 ("margin", C.c_int32), ("h_baseline", C.c_int32), ("max_expansions", C.c_int32), ("node_capacity", C.c_int32),
@@ -202,6 +211,9 @@ def _abi():
             "bp_rollout_end": (I, [P(BpRolloutDesc), i32, vp, vp, vp, vp, i32, f64, vp]),
             "bp_rollout_finish": (I, [P(BpRolloutDesc), vp, f64, f64, vp]),
             "bp_rollout_minibatch": (I, [P(BpRolloutDesc), u64, i64, i32, i32, P(BpRolloutBatch), vp])},
+        "bp_transitions_add": {   # transition buffer for lock-step envs
+            "bp_transitions_add": (I, [P(BpTransitionsDesc)] + [vp] * 8),
+            "bp_transitions_sample": (I, [P(BpTransitionsDesc), u64, i32, P(BpTransitionsBatch), vp])},
     }
     # (sizeof function, the struct it measures, group, the error when the two disagree); the functions join their groups in the table
     layouts = [("bp_sizeof_config", BpConfig, None, "bp_config layout mismatch between _lib.BpConfig and the library"),
@@ -217,7 +229,11 @@ def _abi():
                ("bp_sizeof_replay_desc", BpReplayDesc, "bp_replay_observe", "bp_replay_desc / bp_replay_batch layout mismatch between _lib and the library"),
                ("bp_sizeof_replay_batch", BpReplayBatch, "bp_replay_observe", "bp_replay_desc / bp_replay_batch layout mismatch between _lib and the library"),
                ("bp_sizeof_rollout_desc", BpRolloutDesc, "bp_rollout_begin", "bp_rollout_desc / bp_rollout_batch layout mismatch between _lib and the library"),
-               ("bp_sizeof_rollout_batch", BpRolloutBatch, "bp_rollout_begin", "bp_rollout_desc / bp_rollout_batch layout mismatch between _lib and the library")]
+               ("bp_sizeof_rollout_batch", BpRolloutBatch, "bp_rollout_begin", "bp_rollout_desc / bp_rollout_batch layout mismatch between _lib and the library"),
+               ("bp_sizeof_transitions_desc", BpTransitionsDesc, "bp_transitions_add",
+                "bp_transitions_desc / bp_transitions_batch layout mismatch between _lib and the library"),
+               ("bp_sizeof_transitions_batch", BpTransitionsBatch, "bp_transitions_add",
+                "bp_transitions_desc / bp_transitions_batch layout mismatch between _lib and the library")]
     table = {name: decl + (group,) for group, fns in groups.items() for name, decl in fns.items()}
     table.update((name, (i32, [], group)) for name, _, group, _ in layouts)
     # entry points of the library that the header does not declare: the diagnostic twins' hooks (tools/, tests of the twins)

@@ -5,6 +5,9 @@ checkpoint trained there loads here with ``load_state_dict(strict=True)`` (tests
 ``ResNet18Extractor`` and ``ActorCriticCnn`` are the networks of the PPO baselines (benchpush_amd/baselines/ppo.py).  The reference builds them from
 torchvision's ``resnet18`` and stable-baselines3's ``ActorCriticCnnPolicy``; neither package is available to this project's build, so the parameter
 names below are argued from the documented structure of the two and are not pinned by a fixture of the reference.
+
+``SacActor``, ``SacCritic`` and ``SacPolicy`` are the networks of the SAC baselines (benchpush_amd/baselines/sac.py), laid out as stable-baselines3's SAC
+``CnnPolicy`` names its parts, under the same caveat.
 """
 import math
 
@@ -12,7 +15,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-__all__ = ["ActorCriticCnn", "BasicBlockBN", "DenseActionSpaceDQN", "ResNet18Extractor", "ResNet18NoNorm", "ResidualBlock"]
+__all__ = ["ActorCriticCnn", "BasicBlockBN", "DenseActionSpaceDQN", "ResNet18Extractor", "ResNet18NoNorm", "ResidualBlock", "SacActor", "SacCritic",
+           "SacPolicy", "squashed_gaussian_log_prob"]
 
 
 class ResidualBlock(nn.Module):
@@ -173,3 +177,95 @@ class ActorCriticCnn(nn.Module):
         """log N(actions; mean, exp(log_std)) summed over the action columns, [N]."""
         var = torch.exp(2.0 * self.log_std)
         return (-((actions - mean) ** 2) / (2.0 * var) - self.log_std - 0.5 * math.log(2.0 * math.pi)).sum(dim=1)
+
+
+LOG_STD_MIN, LOG_STD_MAX = -20.0, 2.0      # stable-baselines3's clamp of the SAC actor's log_std
+SQUASH_EPS = 1e-6                          # its epsilon inside the log of the tanh correction
+
+
+def squashed_gaussian_log_prob(mean, log_std, gaussian_actions):
+    """log-density [N] of ``tanh(gaussian_actions)`` for ``gaussian_actions ~ N(mean, exp(log_std))``: the Gaussian's log-density summed over the
+    action columns minus ``sum log(1 - tanh(u)^2 + 1e-6)``, as stable-baselines3's SquashedDiagGaussianDistribution computes it."""
+    normal = -((gaussian_actions - mean) ** 2) / (2.0 * torch.exp(2.0 * log_std)) - log_std - 0.5 * math.log(2.0 * math.pi)
+    return normal.sum(dim=1) - torch.log(1.0 - torch.tanh(gaussian_actions) ** 2 + SQUASH_EPS).sum(dim=1)
+
+
+def _relu_mlp(w_in, widths, w_out=None):
+    layers = []
+    for w in widths:
+        layers += [nn.Linear(w_in, w), nn.ReLU()]
+        w_in = w
+    if w_out is not None:
+        layers.append(nn.Linear(w_in, w_out))
+    return nn.Sequential(*layers)
+
+
+class SacActor(nn.Module):
+    """The actor of stable-baselines3's SAC ``CnnPolicy`` with the reference's arguments: ``features_extractor`` (ResNet18, 512 features), ``latent_pi``
+    (512 -> 512 -> 256 with ReLU: Linear layers 0 and 2), ``mu`` and a state-dependent ``log_std`` (256 -> action_dim each), the latter clamped to
+    [-20, 2].  `features_extractor` and `net_arch` can be replaced (the CPU tests use a small flat extractor)."""
+
+    def __init__(self, num_input_channels=4, action_dim=1, net_arch=(512, 256), features_extractor=None, features_dim=512):
+        super().__init__()
+        self.action_dim = int(action_dim)
+        self.features_extractor = features_extractor if features_extractor is not None else ResNet18Extractor(num_input_channels)
+        self.latent_pi = _relu_mlp(features_dim, list(net_arch))
+        self.mu = nn.Linear(net_arch[-1], self.action_dim)
+        self.log_std = nn.Linear(net_arch[-1], self.action_dim)
+
+    def forward(self, obs):
+        """(mean [N, A], log_std [N, A] clamped)."""
+        latent = self.latent_pi(self.features_extractor(obs))
+        return self.mu(latent), torch.clamp(self.log_std(latent), LOG_STD_MIN, LOG_STD_MAX)
+
+    def action_log_prob(self, obs, noise=None, generator=None):
+        """A sampled action ``tanh(mean + exp(log_std) * noise)`` [N, A] and its log-probability [N]; `noise` standard normal [N, A] (drawn from
+        `generator` where None)."""
+        mean, log_std = self(obs)
+        if noise is None:
+            noise = torch.randn(mean.shape, dtype=mean.dtype, device=mean.device, generator=generator)
+        u = mean + torch.exp(log_std) * noise
+        return torch.tanh(u), squashed_gaussian_log_prob(mean, log_std, u)
+
+    def deterministic(self, obs):
+        """tanh(mean) [N, A]."""
+        return torch.tanh(self(obs)[0])
+
+
+class SacCritic(nn.Module):
+    """The critic of stable-baselines3's SAC ``CnnPolicy`` (``share_features_extractor=False``): its own ``features_extractor`` and two Q networks
+    ``qf0``, ``qf1``, each (features + action_dim) -> 512 -> 256 -> 1 with ReLU (Linear layers 0, 2 and 4)."""
+
+    def __init__(self, num_input_channels=4, action_dim=1, net_arch=(512, 256), features_extractor=None, features_dim=512):
+        super().__init__()
+        self.features_extractor = features_extractor if features_extractor is not None else ResNet18Extractor(num_input_channels)
+        self.qf0 = _relu_mlp(features_dim + int(action_dim), list(net_arch), 1)
+        self.qf1 = _relu_mlp(features_dim + int(action_dim), list(net_arch), 1)
+
+    def forward(self, obs, actions):
+        """(Q0 [N, 1], Q1 [N, 1])."""
+        x = torch.cat([self.features_extractor(obs), actions], dim=1)
+        return self.qf0(x), self.qf1(x)
+
+
+class SacPolicy(nn.Module):
+    """``actor``, ``critic`` and ``critic_target`` (a copy of the critic that takes no gradient and stays in eval mode), the names of stable-baselines3
+    2.x's SAC policy.  Linear and convolution layers keep torch's default initialisation, as that policy does.  Like the PPO names above, these are argued
+    from the documented structure of the package and are not pinned against it.  `make_extractor`: a callable that returns a fresh extractor with
+    `features_dim` outputs (default: ResNet18Extractor(num_input_channels))."""
+
+    def __init__(self, num_input_channels=4, action_dim=1, net_arch=(512, 256), make_extractor=None, features_dim=512):
+        super().__init__()
+        fe = make_extractor if make_extractor is not None else (lambda: ResNet18Extractor(num_input_channels))
+        self.actor = SacActor(num_input_channels, action_dim, net_arch, fe(), features_dim)
+        self.critic = SacCritic(num_input_channels, action_dim, net_arch, fe(), features_dim)
+        self.critic_target = SacCritic(num_input_channels, action_dim, net_arch, fe(), features_dim)
+        self.critic_target.load_state_dict(self.critic.state_dict())
+        self.critic_target.requires_grad_(False)
+        self.critic_target.eval()
+
+    def train(self, mode=True):
+        """Actor and critic follow `mode`; the target stays in eval mode (its batch-norm statistics are copies of the critic's)."""
+        super().train(mode)
+        self.critic_target.eval()
+        return self

@@ -1,1 +1,1 @@
-"""Baselines of maze-NAMO-v0 (benchpush/baselines/maze_NAMO in the reference): planning_based and ppo."""
+"""Baselines of maze-NAMO-v0 (benchpush/baselines/maze_NAMO in the reference): planning_based, ppo and sac."""

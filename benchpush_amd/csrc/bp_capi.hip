@@ -29,6 +29,7 @@
 #include "bp_asyncq.hpp"
 #include "bp_replay.hpp"
 #include "bp_rollout.hpp"
+#include "bp_transitions.hpp"
 
 // The kernels of a ship-ice / maze handle, one per role, chosen once at load (rigid_kernels): the 8-vertex maze instantiations, the generic pair of a
 // handle with damping (no scheduler), or the ship-ice ones.
@@ -2572,6 +2573,59 @@ int bp_rollout_minibatch(const bp_rollout_desc *d, uint64_t seed, int64_t epoch,
                        (long long)epoch, (long long)j * B, (int)B);
     hipLaunchKernelGGL(k_rollout_rows, dim3(B, rollout_strips(r)), dim3(RPL_COPY_THREADS), 0, st, (const uint4 *)r.obs, (const int *)o.index,
                        (const unsigned char *)o.valid, (long long)r.T * r.E, r.row16, o.obs);
+    return hipGetLastError() == hipSuccess ? BP_OK : BP_EHIP;
+}
+
+// ---- transition buffer for lock-step envs (bp_transitions.hpp): handle-free, the caller owns the memory ----
+int32_t bp_sizeof_transitions_desc(void) { return (int32_t)sizeof(bp_transitions_desc); }
+int32_t bp_sizeof_transitions_batch(void) { return (int32_t)sizeof(bp_transitions_batch); }
+static int trans_strips(const TransBuf &r, int64_t rows)   // workgroups per row: RLO_ROW_STRIPS, more while rows * strips stays below TRN_MIN_GROUPS
+{
+    const int64_t pieces = ((int64_t)r.row16 + RPL_COPY_THREADS - 1) / RPL_COPY_THREADS;
+    int64_t want = (TRN_MIN_GROUPS + rows - 1) / rows;
+    if (want < RLO_ROW_STRIPS) want = RLO_ROW_STRIPS;
+    return (int)(pieces < want ? pieces : want);
+}
+static int trans_buf(const bp_transitions_desc *d, TransBuf *r)
+{
+    if (!d || !d->obs || !d->next_obs || !d->action || !d->reward || !d->done || !d->timeout || !d->hdr) return BP_EINVAL;
+    if (d->steps < 1 || d->num_envs < 1 || d->action_dim < 1 || d->device < 0) return BP_EINVAL;
+    if ((int64_t)d->steps * d->num_envs > 0x7FFFFFFFll || (int64_t)d->num_envs * d->action_dim > 0x7FFFFFFFll) return BP_EINVAL;
+    if (d->row_bytes < 16 || d->row_bytes % 16 != 0 || d->row_bytes / 16 > 0x7FFFFFFFll) return BP_EINVAL;
+    if (((((uintptr_t)d->obs) | ((uintptr_t)d->next_obs)) & 15u) != 0) return BP_EINVAL;
+    r->T = d->steps; r->E = d->num_envs; r->A = d->action_dim; r->row16 = (int)(d->row_bytes / 16);
+    r->obs = (uint4 *)d->obs; r->next_obs = (uint4 *)d->next_obs; r->action = d->action; r->reward = d->reward; r->done = d->done;
+    r->timeout = d->timeout; r->hdr = (long long *)d->hdr;
+    return BP_OK;
+}
+int bp_transitions_add(const bp_transitions_desc *d, const uint8_t *obs, const uint8_t *next_obs, const uint8_t *terminal_obs, const float *action,
+                       const double *reward, const uint8_t *done, const uint8_t *truncated, void *stream)
+{
+    TransBuf r;
+    if (trans_buf(d, &r) != BP_OK || !obs || !next_obs || !terminal_obs || !action || !reward || !done || !truncated) return BP_EINVAL;
+    if (((((uintptr_t)obs) | ((uintptr_t)next_obs) | ((uintptr_t)terminal_obs)) & 15u) != 0) return BP_EINVAL;
+    DevGuard dg(d->device);
+    if (!dg.ok) return BP_EHIP;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_trans_rows, dim3(r.E, trans_strips(r, r.E)), dim3(RPL_COPY_THREADS), 0, st, r, (const uint4 *)obs, (const uint4 *)next_obs,
+                       (const uint4 *)terminal_obs, (const unsigned char *)done);
+    hipLaunchKernelGGL(k_trans_scalars, dim3(1), dim3(RPL_THREADS), 0, st, r, action, reward, (const unsigned char *)done, (const unsigned char *)truncated);
+    return hipGetLastError() == hipSuccess ? BP_OK : BP_EHIP;
+}
+int bp_transitions_sample(const bp_transitions_desc *d, uint64_t seed, int32_t B, const bp_transitions_batch *out, void *stream)
+{
+    TransBuf r;
+    if (trans_buf(d, &r) != BP_OK || !out || B < 1) return BP_EINVAL;
+    if (!out->obs || !out->next_obs || !out->action || !out->reward || !out->done || !out->slot || !out->valid) return BP_EINVAL;
+    if (((((uintptr_t)out->obs) | ((uintptr_t)out->next_obs)) & 15u) != 0 || (int64_t)B * d->action_dim > 0x7FFFFFFFll) return BP_EINVAL;
+    TransBatch o;
+    o.obs = out->obs; o.next_obs = out->next_obs; o.action = out->action; o.reward = out->reward; o.done = out->done; o.slot = out->slot;
+    o.valid = out->valid;
+    DevGuard dg(d->device);
+    if (!dg.ok) return BP_EHIP;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_trans_pick, dim3(1), dim3(RPL_THREADS), 0, st, r, o, (int)B, (unsigned long long)seed);
+    hipLaunchKernelGGL(k_trans_gather, dim3(B, trans_strips(r, B), 2), dim3(RPL_COPY_THREADS), 0, st, r, o);
     return hipGetLastError() == hipSuccess ? BP_OK : BP_EHIP;
 }
 

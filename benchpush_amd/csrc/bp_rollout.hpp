@@ -96,20 +96,19 @@ __global__ __launch_bounds__(RPL_THREADS) void k_rollout_pick(const RolloutBuf r
     if (tid == 0 && base > (unsigned)K) r.hdr[0] += (long long)(base - (unsigned)K);
 }
 
-// Grid (rows, strips): row k of `out` is row ids[k] of `src` as floats, (float)u8 / 255.0f by IEEE division from a 256-entry table the workgroup makes by
-// dividing; a lane reads 16 bytes and writes four float4 per turn, the row's pieces dealt to the strips in turns of 256.  Zeros for ids[k] outside
-// [0, limit) or valid[k] == 0 (valid may be NULL).
-__global__ __launch_bounds__(RPL_COPY_THREADS) void k_rollout_rows(const uint4 *__restrict__ src, const int *__restrict__ ids,
-                                                                   const unsigned char *__restrict__ valid, const long long limit, const int row16,
-                                                                   float *__restrict__ out)
+// The 256-entry table tab[u] = (float)u / 255.0f, an IEEE division, made by the 256 threads of a workgroup (RPL_COPY_THREADS) by dividing.
+__device__ __forceinline__ void rlo_u8_table(float *tab)
 {
-    __shared__ float tab[256];
     tab[threadIdx.x] = (float)threadIdx.x / 255.0f;
     __syncthreads();
-    const int k = blockIdx.x;
-    const long long s = (long long)ids[k];
-    const bool ok = s >= 0 && s < limit && (valid == nullptr || valid[k] != 0);
-    for (int p = blockIdx.y * RPL_COPY_THREADS + threadIdx.x; p < row16; p += gridDim.y * RPL_COPY_THREADS) {
+}
+
+// Row `s` of `src` as floats into row `k` of `out`, this workgroup's share: the row's pieces are dealt to `strips` workgroups in turns of 256, a lane reads
+// 16 bytes and writes four float4 per turn.  Zeros where !ok (workgroup-uniform; nothing is read then).
+__device__ __forceinline__ void rlo_float_row(const float *tab, const uint4 *__restrict__ src, const long long s, const bool ok, const int row16,
+                                              float *__restrict__ out, const int k, const int strip, const int strips)
+{
+    for (int p = strip * RPL_COPY_THREADS + threadIdx.x; p < row16; p += strips * RPL_COPY_THREADS) {
         uint4 v = make_uint4(0u, 0u, 0u, 0u);
         if (ok) v = src[(size_t)s * row16 + p];
         const unsigned w[4] = {v.x, v.y, v.z, v.w};
@@ -118,6 +117,21 @@ __global__ __launch_bounds__(RPL_COPY_THREADS) void k_rollout_rows(const uint4 *
             o[c] = ok ? make_float4(tab[w[c] & 255u], tab[(w[c] >> 8) & 255u], tab[(w[c] >> 16) & 255u], tab[(w[c] >> 24) & 255u])
                       : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     }
+}
+
+// Grid (rows, strips): row k of `out` is row ids[k] of `src` as floats, (float)u8 / 255.0f by IEEE division from a 256-entry table the workgroup makes by
+// dividing; a lane reads 16 bytes and writes four float4 per turn, the row's pieces dealt to the strips in turns of 256.  Zeros for ids[k] outside
+// [0, limit) or valid[k] == 0 (valid may be NULL).
+__global__ __launch_bounds__(RPL_COPY_THREADS) void k_rollout_rows(const uint4 *__restrict__ src, const int *__restrict__ ids,
+                                                                   const unsigned char *__restrict__ valid, const long long limit, const int row16,
+                                                                   float *__restrict__ out)
+{
+    __shared__ float tab[256];
+    rlo_u8_table(tab);
+    const int k = blockIdx.x;
+    const long long s = (long long)ids[k];
+    const bool ok = s >= 0 && s < limit && (valid == nullptr || valid[k] != 0);
+    rlo_float_row(tab, src, s, ok, row16, out, k, (int)blockIdx.y, (int)gridDim.y);
 }
 
 // end: reward[t][e] = (float)reward[e] and last_done = done for every env; then, after a barrier, the bootstrap rows: reward[t][e] += g * boot_values[k]

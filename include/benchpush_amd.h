@@ -852,6 +852,46 @@ int bp_rollout_end(const bp_rollout_desc *d, int32_t t, const double *reward, co
 int bp_rollout_finish(const bp_rollout_desc *d, const float *last_values, double gamma, double gl, void *stream);
 int bp_rollout_minibatch(const bp_rollout_desc *d, uint64_t seed, int64_t epoch, int32_t j, int32_t B, const bp_rollout_batch *out, void *stream);
 
+/* ---- transition buffer for lock-step envs (DESIGN.md "Transition buffer") ----
+ * Handle-free: the caller owns every array (device memory on `device`) and passes them in a bp_transitions_desc.  T = steps, E = num_envs, A = action_dim,
+ * R = row_bytes (a multiple of 16; the rows are uint8 and their shape is opaque to the library; every observation array is 16-byte aligned), T * E at most
+ * 2^31 - 1.  A ring of T step rows of E envs:
+ *   obs, next_obs uint8 [T][E][R]; action float [T][E][A]; reward float [T][E]; done, timeout uint8 [T][E]
+ *   hdr int64 [2]: hdr[0] adds ever made, hdr[1] sample draws made
+ * All of it starts as zeros.  Transition (s, e), s the number of adds before it, lives in slot (s % T) * E + e.
+ *
+ * bp_transitions_add writes step row hdr[0] % T (read on the device): obs = obs[e]; next_obs = done[e] ? terminal_obs[e] : next_obs[e] (all uint8
+ * [E][R]); action = action (float [E][A]); reward = (float)reward[e] (double [E]); done = done[e] != 0; timeout = done[e] && truncated[e] (uint8 [E]
+ * each).  Then hdr[0] grows by one, in a kernel the stream orders after the copies.  The arguments are consumed in stream order: work enqueued on `stream`
+ * after the call may rewrite them.
+ *
+ * bp_transitions_sample draws B transitions with replacement: n = min(hdr[0], T) * E on the device, sample b takes slot bp_replay_index(seed, hdr[1], b, n),
+ * then hdr[1] grows by one.  out: obs, next_obs float [B][R] ((float)u8 / 255.0f by IEEE division, 16-byte aligned), action float [B][A], reward float [B],
+ * done float [B] = done * (1 - timeout) (a done that the time limit caused does not stop a bootstrap), slot int32 [B], valid uint8 [B] = 1 when n > 0;
+ * with n == 0 every output is zero and slot is -1.
+ *
+ * Nothing synchronises, nothing is read back; all work is enqueued on `stream`.  BP_EINVAL, before anything is launched: a NULL pointer, row_bytes % 16 != 0,
+ * steps, num_envs or action_dim < 1, steps * num_envs > 2^31 - 1, B < 1, an observation array that is not 16-byte aligned.  (Added within ABI 11: the
+ * additions only add.) */
+typedef struct bp_transitions_desc {
+    int32_t steps, num_envs, device, action_dim;
+    int64_t row_bytes;
+    uint8_t *obs, *next_obs;
+    float *action, *reward;
+    uint8_t *done, *timeout;
+    int64_t *hdr;
+} bp_transitions_desc;
+typedef struct bp_transitions_batch {
+    float *obs, *next_obs, *action, *reward, *done;
+    int32_t *slot;
+    uint8_t *valid;
+} bp_transitions_batch;
+int32_t bp_sizeof_transitions_desc(void);
+int32_t bp_sizeof_transitions_batch(void);
+int bp_transitions_add(const bp_transitions_desc *d, const uint8_t *obs, const uint8_t *next_obs, const uint8_t *terminal_obs, const float *action,
+                       const double *reward, const uint8_t *done, const uint8_t *truncated, void *stream);
+int bp_transitions_sample(const bp_transitions_desc *d, uint64_t seed, int32_t B, const bp_transitions_batch *out, void *stream);
+
 const char *bp_last_error(const bp_handle *h);
 int32_t bp_abi_version(void);
 int32_t bp_sizeof_config(void);   /* sizeof(bp_config), so a binding can verify its struct layout */
