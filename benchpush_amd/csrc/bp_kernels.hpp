@@ -509,6 +509,7 @@ __device__ __forceinline__ bool physics_body(const DevParams &P, const DevPtrs &
                 if (ov && pos < BP_KADJ) { gE(E.adj, i * BP_KADJ + pos) = (unsigned short)j; gE(E.hint, i * BP_KADJ + pos) = 0; }
                 cnt += __popcll(m);
             }
+            PROF_FMAX(32, cnt)
             if (cnt > BP_KADJ) { S.err |= BP_ERR_ADJ_OVERFLOW; cnt = BP_KADJ; }
             if (lane == 0) gE(E.adjn, i) = (unsigned char)cnt;
         }

@@ -23,6 +23,16 @@
 #define PROF_MAX(slot, v) { const unsigned long long _v = (unsigned long long)(v); if (lane_id() == 0 && _v > L.prof[slot]) L.prof[slot] = _v; }
 #define PROF_PARAM , unsigned long long &_pt   // a phase of substep() that lives in a function of its own carries the running stamp along
 #define PROF_ARG , _pt
+// Capacity peaks (DESIGN.md "In-kernel capacities"; tests/test_gpu_fuzz_caps.py), fields of slot 22 (the only slot that neither the sub-step's timers and counters, 0 .. 21 and 23 .. 55, nor
+// k_observe's stamps, 56 .. 63, use): bits 0..7 the largest neighbour count refresh_body found (before the clamp to BP_KADJ), 32..39 the same for the list build of
+// a reset, 8..15 the largest colour the solve-order colouring asked for, counted from 1 (before the clamp to 16), 16..23
+// the most arbiter lanes in use right after a hand-over batch, 24..31 the purges of a full neighbour list by a reciprocal insertion.  A launch ADDS its
+// counters to the buffer: the fields are the launch's own only if the buffer was cleared before it and the step ran in one launch (BP_SCHED=0).
+#define PROF_FMAX(shift, v) { unsigned long long _v = (unsigned long long)(v); if (_v > 255ull) _v = 255ull; \
+                              if (lane_id() == 0 && _v > ((L.prof[22] >> (shift)) & 255ull)) L.prof[22] = (L.prof[22] & ~(255ull << (shift))) | (_v << (shift)); }
+#define PROF_PURGE atomicAdd(&L.prof[22], 1ull << 24);   // by the lane that purges
+#define PROF_LPARAM , const LdsCtx &L
+#define PROF_LARG , L
 #else
 #define PROF_DECL
 #define PROF_ACC(slot)
@@ -30,6 +40,10 @@
 #define PROF_MAX(slot, v)
 #define PROF_PARAM
 #define PROF_ARG
+#define PROF_FMAX(shift, v)
+#define PROF_PURGE
+#define PROF_LPARAM
+#define PROF_LARG
 #endif
 
 
@@ -165,7 +179,7 @@ __device__ __forceinline__ bool bb_overlap(double4 a, double4 b)
 }
 
 // Rebuild the neighbour list of body i around its current AABB (uniform call).
-__device__ __forceinline__ void refresh_body(const DevParams &P, const EnvCtx &E, int i, int &err)
+__device__ __forceinline__ void refresh_body(const DevParams &P, const EnvCtx &E, int i, int &err PROF_LPARAM)
 {
     const int lane = lane_id();
     const double4 b = gE(E.bb, i);
@@ -189,6 +203,7 @@ __device__ __forceinline__ void refresh_body(const DevParams &P, const EnvCtx &E
             for (int s2 = 0; s2 < nj; s2++) found = found || (gE(E.adj, j * BP_KADJ + s2) == (unsigned short)i);
             if (!found) {
                 if (nj >= BP_KADJ) { // purge entries of j that no longer fat-overlap j
+                    PROF_PURGE
                     int w = 0;
                     for (int s2 = 0; s2 < nj; s2++) {
                         const int k = gE(E.adj, j * BP_KADJ + s2);
@@ -212,6 +227,7 @@ __device__ __forceinline__ void refresh_body(const DevParams &P, const EnvCtx &E
             }
         }
     }
+    PROF_FMAX(0, cnt)
     if (cnt > BP_KADJ) { err |= BP_ERR_ADJ_OVERFLOW; cnt = BP_KADJ; }
     if (lane == 0) gE(E.adjn, i) = (unsigned char)cnt;
     __syncthreads();
@@ -301,6 +317,7 @@ __device__ __forceinline__ void arbiters_take(const EnvCtx &E, const LdsCtx &L, 
         }
         dr++;
     }
+    PROF_FMAX(16, __popcll(ballot(A.key != ARB_FREE_KEY)))
     if (my_mb >= 0) {
         const d2 *mb = L.mbox + my_mb * 6;
         const d2 mn_ = mb[0], mp10 = mb[1], mp20 = mb[2], mp11 = mb[3], mp21 = mb[4], mh = mb[5];
@@ -600,7 +617,7 @@ __device__ __forceinline__ void substep(const DevParams &P, const EnvCtx &E, con
         while (BP_UNLIKELY(rm != 0)) {
             const int kk = __ffsll((long long)rm) - 1;
             rm &= rm - 1;
-            refresh_body(P, E, L.mv[k0 + kk], S.err);
+            refresh_body(P, E, L.mv[k0 + kk], S.err PROF_LARG);
             PROF_CNT(17, 1)
         }
         PROF_ACC(1)
@@ -1228,6 +1245,7 @@ __device__ __forceinline__ void substep(const DevParams &P, const EnvCtx &E, con
             const unsigned ua = adyn ? (unsigned)L.colmask[a] : 0u, ub = bdyn ? (unsigned)L.colmask[b] : 0u;
             const unsigned used = ua | ub;
             int c = __ffs(~used) - 1;
+            PROF_FMAX(8, c + 1)
             if (c > 15) { c = 15; S.err |= BP_ERR_LEVEL_OVERFLOW; }
             if (adyn) L.colmask[a] = (unsigned short)(ua | (1u << c));
             if (bdyn) L.colmask[b] = (unsigned short)(ub | (1u << c));

@@ -204,6 +204,13 @@ typedef struct orc_env {
     /* stats for design studies */
     long stat_pairs_bb, stat_narrow, stat_arb_sum, stat_moving_sum, stat_arb_max, stat_substeps;
     long stat_hot_sum;
+    /* capacity study (orc_get_caps_stats; tests/fuzz_caps.py): what the HIP sub-step's fixed in-kernel capacities are measured against.
+     * lanes: arbiters in the cached set right after the collision phase, before the persistence filter drops the stale ones (the kernel holds one
+     * arbiter per lane and looks for a free lane at exactly that point); cached: the same set after the filter; slots: bodies that hold a
+     * velocity slot in the kernel within one env step -- the kinematic ship, every body that moves when the step begins, both bodies of every
+     * arbiter that is cached then or created during the step (slots are not returned within a step).  Ship-ice only. */
+    long stat_lanes_max, stat_cached_max, stat_slots_max;
+    uint8_t *slot_mark; int slot_cap, slot_cnt, slot_clear;
     /* maze-NAMO-v0 */
     int wall_collision;        /* sticky flag set by the (1,3) pre_solve handler, maze_NAMO_env.py:203-205 */
     int nwalls; double walls[16][4];
@@ -701,10 +708,39 @@ static void bd_run_presolve(orc_env *E)
     E->nevents = 0;
 }
 
+/* capacity study: mark the bodies that hold a velocity slot in the HIP kernel (see orc_env) */
+static void caps_mark(orc_env *E, int body)
+{
+    if (!E->slot_mark[body]) { E->slot_mark[body] = 1; E->slot_cnt++; }
+}
+static void caps_begin_substep(orc_env *E)
+{
+    if (E->slot_cap < E->nb) {
+        E->slot_mark = (uint8_t *)realloc(E->slot_mark, (size_t)E->nb);
+        E->slot_cap = E->nb; E->slot_clear = 1;
+    }
+    if (!E->slot_clear) return;
+    E->slot_clear = 0;
+    memset(E->slot_mark, 0, (size_t)E->slot_cap);
+    E->slot_cnt = 0;
+    caps_mark(E, 0);
+    for (int i = 1; i < E->nb; i++) {
+        const body_t *b = &E->bodies[i];
+        if (b->v.x != 0.0 || b->v.y != 0.0 || b->w != 0.0 || b->vb.x != 0.0 || b->vb.y != 0.0 || b->wb != 0.0) caps_mark(E, i);
+    }
+}
+static void caps_after_collide(orc_env *E)
+{
+    if (E->narb > E->stat_lanes_max) E->stat_lanes_max = E->narb;
+    for (int k = 0; k < E->narb; k++) { caps_mark(E, E->shapes[E->arbs[k].sa].body); caps_mark(E, E->shapes[E->arbs[k].sb].body); }
+    if (E->slot_cnt > E->stat_slots_max) E->stat_slots_max = E->slot_cnt;
+}
+
 /* pymunk.Space.step(dt) == Chipmunk2D 7.0.3 cpSpaceStep (cpSpaceStep.c), restated */
 static void space_step(orc_env *E, double dt)
 {
     if (dt == 0.0) return;
+    caps_begin_substep(E);
     E->stamp++;
     double prev_dt = E->curr_dt;
     E->curr_dt = dt;
@@ -759,6 +795,7 @@ static void space_step(orc_env *E, double dt)
         qsort(E->active, (size_t)E->nactive, sizeof(int), cmp_u32);
     }
     if (E->kind == 2 && E->nevents) bd_run_presolve(E);
+    caps_after_collide(E);
     /* cpSpaceArbiterSetFilter over the cached arbiter set */
     {
         int w = 0;
@@ -771,6 +808,7 @@ static void space_step(orc_env *E, double dt)
             w++;
         }
         E->narb = w;
+        if (E->narb > E->stat_cached_max) E->stat_cached_max = E->narb;
     }
     /* Solve order.  Chipmunk sweeps its arbiter array in BB-tree/hash order; any fixed order is a valid Gauss-Seidel
      * sweep.  Here: greedy colouring in ascending key order (an arbiter takes the smallest colour not yet used by
@@ -913,7 +951,7 @@ void orc_destroy(orc_env *E)
     if (!E) return;
     free(E->bodies); free(E->shapes); free(E->arbs); free(E->active); free(E->order); free(E->prev_wv);
     free(E->solve); free(E->color); free(E->used); free(E->disc); free(E->dist_map); free(E->wall_map); free(E->dist_raw);
-    free(E->ras_occ); free(E->ras_foot); free(E->ras_orient); free(E->removed); free(E->events);
+    free(E->ras_occ); free(E->ras_foot); free(E->ras_orient); free(E->removed); free(E->events); free(E->slot_mark);
     free(E);
 }
 
@@ -939,6 +977,7 @@ int orc_reset(orc_env *E, int nf, const double *floe_verts, const int *counts, c
     E->order = (int *)calloc((size_t)nf + 1, sizeof(int));
     E->prev_wv = (double *)calloc((size_t)(nf > 0 ? nf : 1) * ORC_MAXV * 2, sizeof(double));
     E->narb = 0; E->nactive = 0; E->stamp = 0; E->curr_dt = 0.0;
+    E->slot_clear = 1;
     E->total_work = 0.0; E->total_ke = 0.0; E->total_impulse = 0.0;
     E->n_post_solve = E->n_contact_pts = E->n_first_contact = 0;
     E->ship_nv = nsv;
@@ -1027,6 +1066,7 @@ void orc_step(orc_env *E, double action, uint8_t *obs, double *reward, int *term
     ship->v = V(cs * P->target_speed + -sn * 0.0, sn * P->target_speed + cs * 0.0);
     int yaw_violated = 0, boundary_violated = 0, boundary_terminal = 0;
     double dts = P->dt / P->steps;
+    E->slot_clear = 1;
     for (int k = 0; k < P->steps; k++) {
         space_step(E, dts);
         if (ship->a <= 0.0 || ship->a >= M_PI) { ship->w = 0.0; yaw_violated = 1; }
@@ -1122,6 +1162,11 @@ void orc_get_stats(const orc_env *E, long *out)
 {
     out[0] = E->stat_substeps; out[1] = E->stat_pairs_bb; out[2] = E->stat_narrow; out[3] = E->stat_arb_sum;
     out[4] = E->stat_arb_max; out[5] = E->stat_moving_sum; out[6] = E->stat_hot_sum; out[7] = E->stat_ncol_max;
+}
+/* peaks of the capacity study (see orc_env): arbiter lanes needed, cached arbiters after the filter, velocity slots per env step */
+void orc_get_caps_stats(const orc_env *E, long *out)
+{
+    out[0] = E->stat_lanes_max; out[1] = E->stat_cached_max; out[2] = E->stat_slots_max;
 }
 void orc_get_info(const orc_env *E, double *info)
 {

@@ -54,7 +54,7 @@ def lib():
         L.orc_observe.argtypes = [C.c_void_p, C.c_void_p]
         L.orc_num_shapes.restype = C.c_int
         L.orc_num_shapes.argtypes = [C.c_void_p]
-        for name in ("orc_get_bodies", "orc_get_mass", "orc_get_stats", "orc_get_info"):
+        for name in ("orc_get_bodies", "orc_get_mass", "orc_get_stats", "orc_get_caps_stats", "orc_get_info"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_void_p]
         L.orc_get_world_polys.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_get_local_polys.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -197,6 +197,13 @@ class OracleShipIce:
         self.L.orc_get_stats(self.h, _p(out))
         return dict(zip(["substeps", "pairs_bb", "narrow", "arb_sum", "arb_max", "moving_sum", "hot_sum", "ncol_max"], out.tolist()))
 
+    def caps_stats(self):
+        """Peaks since the handle was created, in the units of the HIP sub-step's in-kernel capacities (DESIGN.md "In-kernel capacities"): arbiter lanes
+        needed (cached arbiters right after the collision phase), cached arbiters after the persistence filter, velocity slots per env step."""
+        out = np.zeros(3, np.int64)
+        self.L.orc_get_caps_stats(self.h, _p(out))
+        return dict(zip(["lanes_max", "cached_max", "slots_max"], out.tolist()))
+
 
 def sincos(x):
     s, c = C.c_double(), C.c_double()
@@ -323,6 +330,17 @@ class OracleMaze:
         out = np.zeros((self.ns, 9), np.float64)
         self.L.orc_get_shape_states(self.h, _p(out))
         return out
+
+    def stats(self):
+        out = np.zeros(8, np.int64)
+        self.L.orc_get_stats(self.h, _p(out))
+        return dict(zip(["substeps", "pairs_bb", "narrow", "arb_sum", "arb_max", "moving_sum", "hot_sum", "ncol_max"], out.tolist()))
+
+    def caps_stats(self):
+        """OracleShipIce.caps_stats for the maze's space; the slot count is ship-ice's and means nothing here (the maze has 31 bodies, 96 slots)."""
+        out = np.zeros(3, np.int64)
+        self.L.orc_get_caps_stats(self.h, _p(out))
+        return dict(zip(["lanes_max", "cached_max", "slots_max"], out.tolist()))
 
     def maps(self):
         H, W = int(self.params["map_h"] * self.params["m_to_pix"]), int(self.params["map_w"] * self.params["m_to_pix"])

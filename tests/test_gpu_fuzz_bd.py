@@ -8,7 +8,7 @@ of the reset, and most steps leave through the STEP_LIMIT path).  Bar: `==` afte
 binary64 state of every live shape and the alive mask; the four observation channels byte for byte at reset and after the last step.  The oracle side of
 a case is computed once and shared by the kernel variants (default, single pass, second pass, no recurrence shortcut; damping 0.8 has its own).
 
-An env whose in-kernel capacity flags (BP_ERR_*: BP_KADJ 24, BP_EVCAP 32, BP_NSLOT 96 -- unconstrained piles can reach them by design) are set is printed
+An env whose in-kernel capacity flags (BP_ERR_*: the neighbour, velocity-slot and arbiter capacities of DESIGN.md "In-kernel capacities" and box-delivery's BP_EVCAP -- unconstrained piles can reach them by design) are set is printed
 and left out from that step on; at most 2 % of a case's scenes may go that way.  Nothing else is left out.
 
 A case takes 0.2 - 3 s on the GPU machine (all 28 together 36 s), 1 - 2 s of a default variant the oracle (DESIGN.md "Differential fuzz of the box-delivery / area-clearing step" has the
